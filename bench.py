@@ -21,7 +21,12 @@ step (T = 1, the gym one-call-per-step contract).
 Buffers: K launches cycle through up to 8 distinct action tiles [T, N] and 2 output tiles (a
 consumer reads each launch's outputs before the next one but one), so any K fits in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--env-steps 2000]
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds what
+takes runs of its own: the CPU baselines on the host cores beside the GPU number (``cpu_baseline``,
+``gpu_vs_cpu``) and, for c4, the achievable HBM bandwidth measured in the same run.
+``--dump-outputs DIR`` writes what the last timed step computed (dump_outputs).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--env-steps 2000] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU)
 """
 from __future__ import annotations
@@ -91,8 +96,14 @@ def parse():
     ap.add_argument("--placement", default="auto", choices=["auto", "hash", "xcd"],
                     help="first puzzle of each env (initial_puzzles): auto = xcd past 1,024 puzzles")
     ap.add_argument("--max-steps", type=int, default=2000)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines beside the GPU "
+                         "number and, for the observation-plane configs, this box's achievable HBM bandwidth")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU-baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/<name>.npy (float32; arrays past "
+                         "the budget as a fixed seeded sample)")
     ap.add_argument("--stats-out", default="",
                     help="rank 0 saves the gathered per-env stats [world*N, 4] int32 here (.npy; tests)")
     a = ap.parse_args()
@@ -370,6 +381,29 @@ def achievable_bw(dev, gib=2, reps=10):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # everything --dump-outputs writes, as float32 (under 64 MB)
+DUMP_SEED = 4321
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor) as path/<name>.npy in float32 (exact
+    for these integer codes and counts).  Every array gets an equal share of DUMP_BUDGET_BYTES; a
+    larger one is written as its elements at fixed flat indices (numpy default_rng(DUMP_SEED) of
+    the array's size, sorted, repeats allowed), so two runs with the same arguments write the same
+    elements."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (4 * max(1, len(arrays)))
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), share, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        else:
+            flat = flat.reshape(t.shape)
+        np.save(os.path.join(path, f"{name}.npy"), flat.to(torch.float32).cpu().numpy())
+
+
 def csrc_hash():
     """sha256 (16 hex) of the kernel sources + ABI header + Makefile: the build a committed
     counter summary belongs to."""
@@ -595,6 +629,15 @@ def main():
 
     if rank == 0 and args.stats_out:
         np.save(args.stats_out, gathered.cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        # what the last timed launch returned to its caller (rank 0's shard) and the gathered stats
+        last = (W + K - 1) % RO
+        dumped = {"reward_code": rew[last], "flags": flags[last], "stats": gathered}
+        if rules:
+            dumped["rule_bits"] = rbits[last]
+        if obs and args.mode == "rollout":
+            dumped.update(visited=ovis, agent_location=oag)
+        dump_outputs(args.dump_outputs, dumped)
     kern_ms = [a.elapsed_time(b) for (a, b), _ in events]
     steps_per_launch = [c for _, c in events]
     avg_ms = float(np.mean(kern_ms))
@@ -645,8 +688,8 @@ def main():
                  "note": "VALU issue roofline: SQ_INSTS_VALU of the committed PMC pass / the live kernel time / "
                          "(1,024 SIMDs x one wave64 VALU per 2 cycles x 2.4 GHz)"}
     # the HBM-bound configuration (observation planes: ~99 % of its bytes are plane stores) gets
-    # this box's achievable store bandwidth beside the 8 TB/s peak
-    ach = achievable_bw(dev) if obs and args.mode == "rollout" else None
+    # this box's achievable store bandwidth beside the 8 TB/s peak (a run of its own: --full)
+    ach = achievable_bw(dev) if args.full and obs and args.mode == "rollout" else None
     backend = dist.get_backend() if dist.is_initialized() else None
     observed_world = dist.get_world_size() if dist.is_initialized() else 1
     out = {
@@ -706,10 +749,10 @@ def main():
     }
     if world > 1:
         dist.destroy_process_group()
-    # the CPU step() beside the GPU number at EVERY world size (north_star: "next to the reference
+    # --full: the CPU step() beside the GPU number at EVERY world size (north_star: "next to the reference
     # Python CPU step() timed on the host cores of the same box in the same run"): rank 0, after
     # the timed region and the final barrier, on the host cores the job has (cpu_procs)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         procs = cpu_procs(len(set(pci)))   # the GPUs the job drives (a rehearsal shares one)
         if rules:
             cb = cpu_baseline_rules(proc, tb, args.max_steps, args.cpu_seconds, procs)

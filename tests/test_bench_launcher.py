@@ -101,3 +101,32 @@ def test_cpu_baseline_names_its_cores():
     cb = bench.cpu_baseline(proc, True, 2000, 0.5, None, "c3", procs=2)
     assert cb["cores"] == 2 and cb["value"] > 0 and cb["value_1core"] > 0
     assert "2 processes" in cb["sample"]
+
+
+def test_plain_run_options(monkeypatch):
+    """A plain run asks for none of the extra legs: --full is off by default and on when given."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs == "" and (a.steps, a.warmup) == (5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_float32_within_budget_and_repeatable(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole in their own shape, larger ones as the same seeded sample
+    of their elements on every call, everything float32 within the byte budget."""
+    import numpy as np
+    torch = pytest.importorskip("torch")
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 2 * 1000)   # 1,000 elements per array
+    big = (torch.arange(50000, dtype=torch.int32) % 251 - 100).to(torch.int8).reshape(50, 1000)
+    small = torch.arange(-6, 6, dtype=torch.int32).reshape(3, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = (np.load(tmp_path / d / "big.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (1000,) and np.array_equal(a, b)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, big.numel(), 1000, dtype=np.int64))
+    assert np.array_equal(a, big.reshape(-1).numpy()[idx].astype(np.float32))
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy().astype(np.float32))
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in ("big.npy", "small.npy")) <= 4 * 2 * 1000

@@ -51,7 +51,7 @@ def test_two_rank_hip_rollout_equals_single_process(on_gpu, tmp_path):
 
 def _bench_cmd(*extra, cpu=False):
     return [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"),
-            *(["--cpu-seconds", "1"] if cpu else ["--no-cpu-baseline"]),
+            *(["--full", "--cpu-seconds", "1"] if cpu else ["--no-cpu-baseline"]),
             "--steps", "2", "--warmup", "1", "--env-steps", "64", "--envs", "4096"] + list(extra)
 
 
