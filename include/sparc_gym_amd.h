@@ -255,6 +255,67 @@ int sparc_set_visited_host(void *ctx, const uint64_t *visited);
  *        3 step [N] u32, 4 puzzle [N] u32, 5 direction stack [2*words][N] u64 (traceback) */
 int sparc_state_ptr(void *ctx, int32_t which, void **d_ptr);
 
+/* ---- snapshot, restore and fork of the env state -----------------------------------------------
+ * The reference has no counterpart: its user copies the SPaRC_Gym object to try a continuation
+ * and come back (the per-episode fields _load_puzzle sets, SPaRC_Gym.py:141-187: the visited
+ * plane, path, _agent_location, current_step, current_puzzle_index, outcome_reward).  Here a
+ * snapshot is M opaque fixed-size RECORDS, one per env, in caller-owned memory.  A record holds
+ * everything the step kernels keep for one env between launches, bit for bit: the state arrays of
+ * sparc_state_ptr (visited board, direction stack, pos, aux incl. the solution-trie node and the
+ * off-path depth, step, puzzle).  Its size, record_bytes, is a multiple of 16 and depends on
+ * `words` and `traceback` only: 16 + 8 * words (+ 16 * words with traceback), rounded up; e.g.
+ * words 1 with traceback: 16 + 8 + 16 = 40 -> 48 bytes.  Layout in u32 words: pos, aux, step,
+ * puzzle, visited [words] u64, direction stack [2 * words] u64 (traceback), zero padding.
+ * The per-env exact-fit memo of the rule audit is a cache keyed by (puzzle, region), valid for
+ * any env, and is not part of a record.
+ *
+ * sparc_snapshot_info describes the records of a context; a restore takes it back and is rejected
+ * (SPARC_E_INVALID, message naming the field, state untouched) when words, pitch, traceback,
+ * max_steps, record_bytes or table_hash differ from the context's.  table_hash is a 64-bit FNV-1a
+ * hash of the host arrays given to sparc_load_puzzles (open, info, trie, their counts, pitch,
+ * words).  max_steps is compared because not every step path has been shown to read `step` only
+ * through `step >= max_steps`.  autoreset is a property of the context, not of the state (the
+ * state holds only the pending bit, set in both modes): a snapshot of a NONE context restores into
+ * a NEXT_STEP one, and its pending envs then autoreset on their next step. */
+#define SPARC_SNAPSHOT_MAGIC 0x53525053u   /* "SPRS" */
+typedef struct {
+    uint32_t magic;         /* SPARC_SNAPSHOT_MAGIC                                  */
+    int32_t abi_version;    /* SPARC_ABI_VERSION                                     */
+    int32_t words;
+    int32_t pitch;
+    int32_t traceback;
+    int32_t max_steps;
+    int32_t record_bytes;
+    int32_t reserved;       /* 0                                                     */
+    uint64_t table_hash;
+} sparc_snapshot_info;
+/* what a snapshot of this context looks like (after sparc_load_puzzles) */
+int sparc_snapshot_info_get(void *ctx, sparc_snapshot_info *out);
+/* Record j <- the state of env d_env[j], j < M (d_env NULL: env j, and M must equal num_envs).
+ * d_records: M * record_bytes bytes, 16-B aligned.  Device pointers, asynchronous.  An index not
+ * below num_envs gives a zeroed record (which no restore accepts) and an error at sparc_sync. */
+int sparc_snapshot_device(void *ctx, const uint32_t *d_env, int64_t M, void *d_records);
+/* Env i with d_mask[i] != 0 (NULL: all) <- record d_src[i] (NULL: record i, and M must equal
+ * num_envs).  d_flags (may be NULL) receives, for the restored envs only, the legal actions of the
+ * restored state in bits 2-5, as sparc_reset_device.  Checked on the device before anything is
+ * dereferenced: d_src[i] < M, and the record's puzzle < num_puzzles, trie node below that puzzle's
+ * node count, x < x_size, y < y_size, 1 <= path length <= lattice points; an env that fails keeps
+ * its state and sparc_sync reports the error.  Like a reset, the first state-writing call on a
+ * context must cover every env (d_mask NULL).  Device pointers, asynchronous. */
+int sparc_restore_device(void *ctx, const sparc_snapshot_info *info, const void *d_records, int64_t M,
+                         const uint32_t *d_src, const uint8_t *d_mask, uint8_t *d_flags);
+/* Env i with d_mask[i] != 0 (NULL: all) <- the state of env d_src[i] of the same context, as ONE
+ * simultaneous assignment: every read sees the state from before the call, for any d_src
+ * (permutations, cycles, fan-out).  Runs through a context-owned scratch of records (snapshot,
+ * then restore), so the pointers of sparc_state_ptr stay valid.  d_src[i] >= num_envs: env i keeps
+ * its state, error at sparc_sync.  d_flags as sparc_restore_device.  Asynchronous. */
+int sparc_fork_device(void *ctx, const uint32_t *d_src, const uint8_t *d_mask, uint8_t *d_flags);
+/* the host-pointer forms: staged through the context's stream, return after the data have moved
+ * (flags of envs not restored read 0) */
+int sparc_snapshot_host(void *ctx, const uint32_t *env, int64_t M, void *records);
+int sparc_restore_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
+                       const uint32_t *src, const uint8_t *mask, uint8_t *flags);
+
 /* ---- rule audit: info['rule_status'] (_validate_rules, SPaRC_Gym.py:941-950) ----------------
  * Rule table, packed by sparc_gym_amd/puzzles.py:pack_rules from the processed puzzles, on the
  * step table's geometry (bit x*pitch + y, `words` u64 per board).

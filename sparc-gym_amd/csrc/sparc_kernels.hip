@@ -8,6 +8,7 @@
 //              Final_Product.py:26-38 / llm_host.py:182-242, batched)
 //   k_obs_pack dense int32 visited / agent_location planes         (_get_obs, SPaRC_Gym.py:979)
 //   k_rules    rule audit of the current state                      (_validate_rules, 941-950)
+//   k_snapshot / k_restore  the state as per-env records and back  (sparc_snapshot.hpp)
 // No MFMA: this is integer / bitboard work, bound by latency and HBM.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -28,6 +29,7 @@
 #include "sparc_movew.hpp"
 #include "sparc_move1.hpp"
 #include "sparc_rules.hpp"
+#include "sparc_snapshot.hpp"
 #include "sparc_gym_amd.h"
 
 using namespace sparc;
@@ -2015,6 +2017,13 @@ struct Ctx {
     // the state a generic rule rollout started from (re-run on a queue overflow)
     void* snap = nullptr;
     size_t snap_bytes = 0;
+    // snapshot / restore / fork (sparc_snapshot.hpp): hash of the loaded table's host arrays, and
+    // scratch that grows on demand: records (fork, the *_host forms) and an index list
+    uint64_t table_hash = 0;
+    void* fk_rec = nullptr;
+    size_t fk_rec_bytes = 0;
+    uint32_t* fk_idx = nullptr;
+    size_t fk_idx_bytes = 0;
     uint16_t* s_bits = nullptr;
     uint8_t* s_region = nullptr;
     uint64_t* s_fit = nullptr;
@@ -2267,6 +2276,8 @@ int sparc_destroy(void* ctx) {
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (c->snap) (void)hipFree(c->snap);
+    if (c->fk_rec) (void)hipFree(c->fk_rec);
+    if (c->fk_idx) (void)hipFree(c->fk_idx);
     if (c->h_count) (void)hipHostFree(c->h_count);
     if (c->h_rec) (void)hipHostFree(c->h_rec);
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -2303,6 +2314,8 @@ int sparc_sync(void* ctx) {
         if (e & 2) return fail(c, SPARC_E_STATE, "device-side trie node out of range (state corrupted)");
         if (e & 8) return fail(c, SPARC_E_STATE, "rule audit: env puzzle index outside the rule table");
         if (e & kErrJoin) return fail(c, SPARC_E_STATE, "rule rollout: an audit wave pair did not join (outputs unreliable)");
+        if (e & kErrSnapshot)
+            return fail(c, SPARC_E_INVALID, "snapshot / restore / fork: index or record out of range (those envs unchanged)");
         return fail(c, SPARC_E_INVALID, "device-side puzzle index out of range in a reset");
     }
     return SPARC_OK;
@@ -2640,6 +2653,20 @@ int sparc_load_puzzles(void* ctx, const sparc_puzzle_table* t) {
     c->num_puzzles = (uint32_t)t->num_puzzles;
     c->num_nodes = (uint32_t)t->num_nodes;
     c->h_info.assign(t->info, t->info + 4 * P);
+    // identity of the table for snapshots (sparc_snapshot_info): FNV-1a over the host arrays
+    {
+        uint64_t h = 0xCBF29CE484222325ull;
+        auto mix = [&h](const void* d, size_t bytes) {
+            const uint8_t* b = static_cast<const uint8_t*>(d);
+            for (size_t k = 0; k < bytes; ++k) h = (h ^ b[k]) * 0x100000001B3ull;
+        };
+        const int32_t head[4] = {t->num_puzzles, t->num_nodes, c->cfg.pitch, c->cfg.words};
+        mix(head, sizeof head);
+        mix(t->open, sizeof(uint64_t) * P * W);
+        mix(t->info, sizeof(uint32_t) * 4 * P);
+        if (t->num_nodes > 0) mix(t->trie, sizeof(uint32_t) * 4 * (size_t)t->num_nodes);
+        c->table_hash = h;
+    }
     c->loaded = true;
     c->rules = false;       // the rule table indexes the old puzzles
     c->has_state = false;   // old state may point at puzzles that no longer exist
@@ -3799,6 +3826,189 @@ int sparc_copy_state_device(void* ctx, int32_t which, void* d_out) {
     const size_t bytes = which == 0 ? 8 * n * c->W : which == 5 ? 16 * n * c->W : 4 * n;
     HIPCHK(c, hipMemcpyAsync(d_out, src, bytes, hipMemcpyDeviceToDevice, c->stream));
     return SPARC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Snapshot, restore and fork (sparc_snapshot.hpp)
+namespace {
+
+sparc_snapshot_info snapshot_info(const Ctx* c) {
+    sparc_snapshot_info s{};
+    s.magic = SPARC_SNAPSHOT_MAGIC;
+    s.abi_version = SPARC_ABI_VERSION;
+    s.words = c->cfg.words;
+    s.pitch = c->cfg.pitch;
+    s.traceback = c->cfg.traceback;
+    s.max_steps = c->cfg.max_steps;
+    s.record_bytes = snap_record_bytes(c->W, c->cfg.traceback != 0);
+    s.table_hash = c->table_hash;
+    return s;
+}
+
+// device scratch of at least `need` bytes (kept; replaced by a larger one on demand, as Ctx::snap)
+template <class T>
+int grow(Ctx* c, T** buf, size_t* have, size_t need) {
+    if (need <= *have) return SPARC_OK;
+    if (*buf) HIPCHK(c, hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(buf), need));
+    *have = need;
+    return SPARC_OK;
+}
+
+int check_snapshot_info(Ctx* c, const sparc_snapshot_info* in) {
+    if (!in) return fail(c, SPARC_E_INVALID, "null snapshot info");
+    const sparc_snapshot_info me = snapshot_info(c);
+    char m[160];
+    if (in->magic != me.magic) return fail(c, SPARC_E_INVALID, "snapshot mismatch: magic");
+#define SPARC_SNAP_FIELD(f)                                                                                  \
+    if (in->f != me.f) {                                                                                     \
+        snprintf(m, sizeof m, "snapshot mismatch: " #f " (snapshot %lld, context %lld)", (long long)in->f,   \
+                 (long long)me.f);                                                                           \
+        return fail(c, SPARC_E_INVALID, m);                                                                  \
+    }
+    SPARC_SNAP_FIELD(abi_version)
+    SPARC_SNAP_FIELD(words)
+    SPARC_SNAP_FIELD(pitch)
+    SPARC_SNAP_FIELD(traceback)
+    SPARC_SNAP_FIELD(max_steps)
+    SPARC_SNAP_FIELD(record_bytes)
+#undef SPARC_SNAP_FIELD
+    if (in->table_hash != me.table_hash)
+        return fail(c, SPARC_E_INVALID, "snapshot mismatch: table_hash (taken on another puzzle table)");
+    return SPARC_OK;
+}
+
+int check_record_count(Ctx* c, int64_t M, bool identity) {
+    if (M < 1 || M > 0x7FFFFFFFll) return fail(c, SPARC_E_INVALID, "M must be in 1..2^31-1");
+    if (identity && M != (int64_t)c->n) return fail(c, SPARC_E_INVALID, "a NULL index list needs M == num_envs");
+    return SPARC_OK;
+}
+
+int launch_snapshot(Ctx* c, const uint32_t* d_env, uint32_t M, void* d_records) {
+    const Params p = make_params(c);
+    dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
+        k_snapshot<decltype(w)::value, decltype(tb)::value><<<grid_for(M), kSnapBlock, 0, c->stream>>>(
+            p, d_env, M, static_cast<uint4*>(d_records));
+    });
+    return launch_check(c);
+}
+
+int launch_restore(Ctx* c, const void* d_records, uint32_t M, const uint32_t* d_src, const uint8_t* d_mask,
+                   uint8_t* d_flags) {
+    const Params p = make_params(c);
+    dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
+        k_restore<decltype(w)::value, decltype(tb)::value><<<grid_for(c->n), kSnapBlock, 0, c->stream>>>(
+            p, static_cast<const uint4*>(d_records), M, d_src, d_mask, d_flags);
+    });
+    return launch_check(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sparc_snapshot_info_get(void* ctx, sparc_snapshot_info* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c) return fail(nullptr, SPARC_E_INVALID, "null context");
+    if (!out) return fail(c, SPARC_E_INVALID, "null argument");
+    if (!c->loaded) return fail(c, SPARC_E_STATE, "sparc_load_puzzles has not been called");
+    *out = snapshot_info(c);
+    return SPARC_OK;
+}
+
+int sparc_snapshot_device(void* ctx, const uint32_t* d_env, int64_t M, void* d_records) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, true);
+    if (rc) return rc;
+    if (!d_records) return fail(c, SPARC_E_INVALID, "null records");
+    if (reinterpret_cast<uintptr_t>(d_records) & 15u) return fail(c, SPARC_E_INVALID, "records must be 16-B aligned");
+    if ((rc = check_record_count(c, M, d_env == nullptr))) return rc;
+    return launch_snapshot(c, d_env, (uint32_t)M, d_records);
+}
+
+int sparc_restore_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M,
+                         const uint32_t* d_src, const uint8_t* d_mask, uint8_t* d_flags) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_snapshot_info(c, info))) return rc;
+    if (!d_records) return fail(c, SPARC_E_INVALID, "null records");
+    if (reinterpret_cast<uintptr_t>(d_records) & 15u) return fail(c, SPARC_E_INVALID, "records must be 16-B aligned");
+    if ((rc = check_record_count(c, M, d_src == nullptr))) return rc;
+    if (d_mask && !c->has_state)
+        return fail(c, SPARC_E_STATE, "the first state-writing call must cover every env (mask NULL)");
+    if ((rc = launch_restore(c, d_records, (uint32_t)M, d_src, d_mask, d_flags))) return rc;
+    c->has_state = true;
+    return SPARC_OK;
+}
+
+int sparc_fork_device(void* ctx, const uint32_t* d_src, const uint8_t* d_mask, uint8_t* d_flags) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, true);
+    if (rc) return rc;
+    if (!d_src) return fail(c, SPARC_E_INVALID, "null src");
+    const size_t rb = (size_t)snap_record_bytes(c->W, c->cfg.traceback != 0);
+    if ((rc = grow(c, &c->fk_rec, &c->fk_rec_bytes, rb * c->n))) return rc;
+    // record j <- env j for every env (coalesced), then env i <- record d_src[i]: all reads of the
+    // state come first, and the gather reads whole records
+    if ((rc = launch_snapshot(c, nullptr, c->n, c->fk_rec))) return rc;
+    return launch_restore(c, c->fk_rec, c->n, d_src, d_mask, d_flags);
+}
+
+int sparc_snapshot_host(void* ctx, const uint32_t* env, int64_t M, void* records) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, true);
+    if (rc) return rc;
+    if (!records) return fail(c, SPARC_E_INVALID, "null records");
+    if ((rc = check_record_count(c, M, env == nullptr))) return rc;
+    if (env)
+        for (int64_t j = 0; j < M; ++j)
+            if (env[j] >= c->n) return fail(c, SPARC_E_INVALID, "env index out of range");
+    const size_t bytes = (size_t)snap_record_bytes(c->W, c->cfg.traceback != 0) * (size_t)M;
+    if ((rc = grow(c, &c->fk_rec, &c->fk_rec_bytes, bytes))) return rc;
+    if (env) {
+        if ((rc = grow(c, &c->fk_idx, &c->fk_idx_bytes, sizeof(uint32_t) * (size_t)M))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->fk_idx, env, sizeof(uint32_t) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = launch_snapshot(c, env ? c->fk_idx : nullptr, (uint32_t)M, c->fk_rec))) return rc;
+    HIPCHK(c, hipMemcpyAsync(records, c->fk_rec, bytes, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
+}
+
+int sparc_restore_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M,
+                       const uint32_t* src, const uint8_t* mask, uint8_t* flags) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_snapshot_info(c, info))) return rc;
+    if (!records) return fail(c, SPARC_E_INVALID, "null records");
+    if ((rc = check_record_count(c, M, src == nullptr))) return rc;
+    if (mask && !c->has_state)
+        return fail(c, SPARC_E_STATE, "the first state-writing call must cover every env (mask NULL)");
+    if (src)
+        for (uint32_t i = 0; i < c->n; ++i)
+            if ((!mask || mask[i]) && src[i] >= (uint64_t)M) return fail(c, SPARC_E_INVALID, "record index out of range");
+    const size_t bytes = (size_t)info->record_bytes * (size_t)M;
+    if ((rc = grow(c, &c->fk_rec, &c->fk_rec_bytes, bytes))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->fk_rec, records, bytes, hipMemcpyHostToDevice, c->stream));
+    if (src) HIPCHK(c, hipMemcpyAsync(c->s_pidx, src, sizeof(uint32_t) * c->n, hipMemcpyHostToDevice, c->stream));
+    if (mask) HIPCHK(c, hipMemcpyAsync(c->s_mask, mask, c->n, hipMemcpyHostToDevice, c->stream));
+    if (flags) HIPCHK(c, hipMemsetAsync(c->s_flags, 0, c->n, c->stream));
+    rc = sparc_restore_device(c, info, c->fk_rec, M, src ? c->s_pidx : nullptr, mask ? c->s_mask : nullptr,
+                              flags ? c->s_flags : nullptr);
+    if (rc) return rc;
+    if (flags) HIPCHK(c, hipMemcpyAsync(flags, c->s_flags, c->n, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
 }
 
 }  // extern "C"

@@ -51,6 +51,18 @@ class SparcEnvRecord(ctypes.Structure):
 
 assert ctypes.sizeof(SparcEnvRecord) == 320
 
+SNAPSHOT_MAGIC = 0x53525053   # SPARC_SNAPSHOT_MAGIC
+
+
+class SparcSnapshotInfo(ctypes.Structure):
+    """sparc_snapshot_info: what the records of a snapshot look like and which table they index."""
+    _fields_ = [("magic", ctypes.c_uint32), ("abi_version", ctypes.c_int32), ("words", ctypes.c_int32),
+                ("pitch", ctypes.c_int32), ("traceback", ctypes.c_int32), ("max_steps", ctypes.c_int32),
+                ("record_bytes", ctypes.c_int32), ("reserved", ctypes.c_int32), ("table_hash", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(SparcSnapshotInfo) == 40
+
 
 _SIGS = {
     "sparc_abi_version": ([], c_int32),
@@ -85,6 +97,14 @@ _SIGS = {
     "sparc_state_ptr": ([c_void_p, c_int32, ctypes.POINTER(c_void_p)], c_int32),
     "sparc_set_visited_host": ([c_void_p, c_void_p], c_int32),
     "sparc_copy_state_device": ([c_void_p, c_int32, c_void_p], c_int32),
+    "sparc_snapshot_info_get": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo)], c_int32),
+    "sparc_snapshot_device": ([c_void_p, c_void_p, ctypes.c_int64, c_void_p], c_int32),
+    "sparc_restore_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_void_p,
+                              c_void_p, c_void_p], c_int32),
+    "sparc_fork_device": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),
+    "sparc_snapshot_host": ([c_void_p, c_void_p, ctypes.c_int64, c_void_p], c_int32),
+    "sparc_restore_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_void_p,
+                            c_void_p, c_void_p], c_int32),
     "sparc_load_rules": ([c_void_p, ctypes.POINTER(SparcRulesTable)], c_int32),
     "sparc_rules_device": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_rules_host": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),

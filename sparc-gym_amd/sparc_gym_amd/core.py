@@ -236,6 +236,48 @@ class SparcCore:
     def obs_pack_device(self, d_visited, d_agent, x_dim, y_dim):
         self._check(self.lib.sparc_obs_pack_device(self.ctx, d_visited, d_agent, int(x_dim), int(y_dim)))
 
+    # ---------------------------------------------------------------- snapshot / restore / fork
+    def snapshot_info(self):
+        """sparc_snapshot_info of this context: record size, shape and the loaded table's hash."""
+        info = _lib.SparcSnapshotInfo()
+        self._check(self.lib.sparc_snapshot_info_get(self.ctx, ctypes.byref(info)))
+        return info
+
+    def snapshot_device(self, d_env, M, d_records):
+        self._check(self.lib.sparc_snapshot_device(self.ctx, d_env, int(M), d_records))
+
+    def restore_device(self, info, d_records, M, d_src=None, d_mask=None, d_flags=None):
+        self._check(self.lib.sparc_restore_device(self.ctx, ctypes.byref(info), d_records, int(M), d_src, d_mask,
+                                                  d_flags))
+        self.has_state = True
+
+    def fork_device(self, d_src, d_mask=None, d_flags=None):
+        self._check(self.lib.sparc_fork_device(self.ctx, d_src, d_mask, d_flags))
+
+    def snapshot_host(self, envs=None):
+        """Records [M, record_bytes] uint8 on the host: of env envs[j], or of every env."""
+        e = None if envs is None else np.ascontiguousarray(envs, np.uint32)
+        if e is not None and e.ndim != 1:
+            raise ValueError("envs must be one-dimensional")
+        M = self.num_envs if e is None else len(e)
+        rec = np.empty((M, self.snapshot_info().record_bytes), np.uint8)
+        self._check(self.lib.sparc_snapshot_host(self.ctx, _ptr(e), M, _ptr(rec)))
+        return rec
+
+    def restore_host(self, info, records, src=None, mask=None):
+        """Restore host records; returns the flags [N] uint8 (legal actions << 2, 0 if not restored)."""
+        rec = np.ascontiguousarray(records, np.uint8)
+        s = None if src is None else np.ascontiguousarray(src, np.uint32)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        for a, what in ((s, "src"), (m, "mask")):
+            if a is not None and a.shape != (self.num_envs,):
+                raise ValueError(f"{what} must have shape ({self.num_envs},)")
+        flags = np.zeros(self.num_envs, np.uint8)
+        self._check(self.lib.sparc_restore_host(self.ctx, ctypes.byref(info), _ptr(rec), len(rec), _ptr(s), _ptr(m),
+                                                _ptr(flags)))
+        self.has_state = True
+        return flags
+
 
 def visited_planes(bits, table: PuzzleTable, x_dim=None, y_dim=None):
     """Decode visited bitboards [words][N] into int32 planes [N][x_dim][y_dim] (host)."""

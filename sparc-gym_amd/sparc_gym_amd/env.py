@@ -385,6 +385,15 @@ class SPaRC_Gym(Env):
                 "rule_status": self.rule_status,
                 "Rewards": {"normal_reward": self.normal_reward, "outcome_reward": self.outcome_reward}}
 
+    def snapshot(self):
+        """The env's device state as a one-record ``Snapshot`` (the reference's counterpart is a
+        copy of the env object, fields SPaRC_Gym.py:141-187).  A position reached interactively
+        can be fanned out into a batch with ``SPaRCVecEnv.restore(snap, src=zeros)`` on the same
+        puzzles, ``traceback`` and ``max_steps``.  Restoring INTO a SPaRC_Gym is not offered: its
+        host-side ``path`` list cannot be rebuilt from a record without traceback."""
+        from .snapshot import Snapshot
+        return Snapshot(self._core.snapshot_host(), self._core.snapshot_info())
+
     def render(self):
         return None
 

@@ -1,0 +1,135 @@
+"""Snapshot: the state of M envs as opaque fixed-size records, with the header that says which
+contexts may take them back (include/sparc_gym_amd.h, sparc_snapshot_info).
+
+The reference has no counterpart; its user copies the ``SPaRC_Gym`` object (the per-episode
+fields of ``_load_puzzle``, SPaRC_Gym.py:141-187).  ``SPaRCVecEnv.snapshot()`` returns one of
+these, ``SPaRCVecEnv.restore(snap, src)`` writes record ``src[i]`` into env ``i``, and
+``save`` / ``load`` keep it in a file.
+
+File format (little endian, numpy only, no pickle)::
+
+    offset  0  8 bytes   b"SPRCSNAP"
+            8  u32       file format version (1)
+           12  u32       header bytes H (40 = sizeof(sparc_snapshot_info))
+           16  u64       M, the number of records
+           24  H bytes   sparc_snapshot_info: magic u32, abi_version, words, pitch, traceback,
+                         max_steps, record_bytes, reserved (i32 each), table_hash u64
+         24+H  M * record_bytes bytes: the records
+          end  u32       zlib.crc32 of the records
+"""
+from __future__ import annotations
+
+import ctypes
+import zlib
+
+import numpy as np
+
+from . import _lib
+
+FILE_MAGIC = b"SPRCSNAP"
+FILE_VERSION = 1
+_HEAD = 24
+INFO_FIELDS = ("words", "pitch", "traceback", "max_steps", "record_bytes", "table_hash")
+
+
+def record_bytes(words, traceback):
+    """Bytes of one record: pos, aux, step, puzzle (16 B), the visited board (8 * words) and,
+    with traceback, the direction stack (16 * words), rounded up to a multiple of 16."""
+    if words not in (1, 2, 4):
+        raise ValueError("words must be 1, 2 or 4")
+    return (16 + 8 * words + (16 * words if traceback else 0) + 15) // 16 * 16
+
+
+def _copy_info(info):
+    out = _lib.SparcSnapshotInfo()
+    ctypes.memmove(ctypes.byref(out), ctypes.byref(info), ctypes.sizeof(out))
+    return out
+
+
+def info_mismatch(a, b):
+    """Name of the first header field in which two sparc_snapshot_info differ, or None."""
+    for f in INFO_FIELDS:
+        if getattr(a, f) != getattr(b, f):
+            return f
+    return None
+
+
+class Snapshot:
+    """``records``: uint8 [M, record_bytes], a torch tensor (GPU or CPU) or a numpy array;
+    ``info``: the ``_lib.SparcSnapshotInfo`` of the context that wrote them."""
+
+    def __init__(self, records, info):
+        if records.ndim != 2 or records.shape[1] != info.record_bytes:
+            raise ValueError(f"records must be [M, {info.record_bytes}] uint8")
+        if info.magic != _lib.SNAPSHOT_MAGIC:
+            raise ValueError("bad snapshot header magic")
+        self.records = records
+        self.info = _copy_info(info)
+
+    def __len__(self):
+        return int(self.records.shape[0])
+
+    @property
+    def is_host(self):
+        return isinstance(self.records, np.ndarray) or self.records.device.type == "cpu"
+
+    def numpy(self):
+        """The records as a C-contiguous numpy array on the host (a copy if they are on the GPU)."""
+        r = self.records
+        if not isinstance(r, np.ndarray):
+            r = r.detach().cpu().numpy()
+        return np.ascontiguousarray(r, np.uint8)
+
+    def cpu(self):
+        if isinstance(self.records, np.ndarray):
+            return self
+        return Snapshot(self.records.cpu(), self.info)
+
+    def to(self, device):
+        import torch
+        r = self.records
+        if isinstance(r, np.ndarray):
+            r = torch.from_numpy(np.ascontiguousarray(r, np.uint8))
+        return Snapshot(r.to(device), self.info)
+
+    # ------------------------------------------------------------------ file
+    def save(self, path):
+        rec = self.numpy()
+        info = bytes(self.info)
+        with open(path, "wb") as f:
+            f.write(FILE_MAGIC)
+            f.write(np.array([FILE_VERSION, len(info)], "<u4").tobytes())
+            f.write(np.array([len(rec)], "<u8").tobytes())
+            f.write(info)
+            f.write(rec.tobytes())
+            f.write(np.array([zlib.crc32(rec.tobytes()) & 0xFFFFFFFF], "<u4").tobytes())
+
+    @classmethod
+    def load(cls, path):
+        """Read a file written by ``save``.  ValueError on a bad magic, a size that does not match
+        the header, or a wrong checksum."""
+        with open(path, "rb") as f:
+            blob = f.read()
+        H = ctypes.sizeof(_lib.SparcSnapshotInfo)
+        if len(blob) < _HEAD + H + 4:
+            raise ValueError("snapshot file too short")
+        if blob[:8] != FILE_MAGIC:
+            raise ValueError("not a snapshot file (bad magic)")
+        version, hbytes = (int(v) for v in np.frombuffer(blob, "<u4", 2, 8))
+        M = int(np.frombuffer(blob, "<u8", 1, 16)[0])
+        if version != FILE_VERSION or hbytes != H:
+            raise ValueError(f"unsupported snapshot file version {version} / header size {hbytes}")
+        info = _lib.SparcSnapshotInfo.from_buffer_copy(blob[_HEAD:_HEAD + H])
+        if info.magic != _lib.SNAPSHOT_MAGIC:
+            raise ValueError("bad snapshot header magic")
+        rb = info.record_bytes
+        if rb < 16 or rb % 16 or info.words not in (1, 2, 4) or rb != record_bytes(info.words, info.traceback):
+            raise ValueError(f"bad record size {rb} in the snapshot header")
+        if len(blob) != _HEAD + H + M * rb + 4:
+            raise ValueError(f"snapshot file size {len(blob)} does not match its header ({M} records of {rb} bytes)")
+        payload = blob[_HEAD + H:_HEAD + H + M * rb]
+        crc = int(np.frombuffer(blob, "<u4", 1, len(blob) - 4)[0])
+        if zlib.crc32(payload) & 0xFFFFFFFF != crc:
+            raise ValueError("snapshot file checksum mismatch")
+        rec = np.frombuffer(payload, np.uint8).reshape(M, rb).copy()
+        return cls(rec, info)

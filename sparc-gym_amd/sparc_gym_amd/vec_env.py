@@ -25,6 +25,11 @@ Rule audit (``rules=True``, or ``rule_audit()`` on demand): the reference's
 as ``info['rule_bits']`` [N] int16 with bit k = ``RULE_NAMES[k]`` passed.  An exact-fit search
 that passes the GPU's node cap (``fit_cap``, default 2^26) is finished on the host without a
 cap, as the reference's unbounded search (sparc_rules_finish): the bits are always final.
+
+Snapshot / restore / fork: ``snapshot()`` returns the state of any envs as opaque records
+(``sparc_gym_amd.Snapshot``), ``restore(snap, src, mask)`` writes record ``src[i]`` into env ``i``
+of any env on the same puzzle table, ``fork(src)`` makes env ``i`` a copy of env ``src[i]``: one
+position fanned out to every env for playouts, beam search or MCTS, or a run saved and resumed.
 """
 from __future__ import annotations
 
@@ -398,6 +403,100 @@ class SPaRCVecEnv:
             raise ValueError(f"out must be a contiguous uint8 tensor [{T}, {n}] on {self.device}")
         self.core.random_actions_device(T, out.data_ptr(), seed, t0)
         return out
+
+    # ------------------------------------------------------------------ snapshot / restore / fork
+    def _index_arg(self, idx, what, limit):
+        """An env / record index list for the device: [len] int32 tensor.  A host-side list or
+        array is range-checked here (ValueError); a tensor is passed through and checked by the
+        kernel (an env with a bad index keeps its state, and the next sync raises)."""
+        if isinstance(idx, torch.Tensor):
+            if idx.ndim != 1 or idx.dtype.is_floating_point or idx.dtype == torch.bool:
+                raise ValueError(f"{what} must be a one-dimensional integer tensor")
+            return idx.to(device=self.device, dtype=torch.int32).contiguous()
+        a = np.asarray(idx)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or a.size == 0:
+            raise ValueError(f"{what} must be a non-empty one-dimensional integer array")
+        if int(a.min()) < 0 or int(a.max()) >= limit:
+            raise ValueError(f"{what} entries must be in [0, {limit})")
+        return torch.from_numpy(a.astype(np.int32)).to(self.device)
+
+    def _mask_arg(self, mask):
+        if mask is None:
+            return None
+        if isinstance(mask, torch.Tensor):
+            m = mask.to(device=self.device)
+        else:
+            m = torch.from_numpy(np.asarray(mask)).to(self.device)
+        if m.shape != (self.num_envs,):
+            raise ValueError(f"mask must have shape ({self.num_envs},)")
+        return (m != 0).to(torch.uint8).contiguous()
+
+    def _restored(self, flags, mask):
+        """(obs, info) after a restore / fork, as reset() returns them."""
+        restored = torch.ones(self.num_envs, dtype=torch.bool, device=self.device) if mask is None else mask.bool()
+        info = {"legal_mask": (flags >> 2) & 0xF, "restored": restored}
+        if self.rules:
+            info["rule_bits"] = self.rule_audit()["bits"]
+        return self._obs(), info
+
+    def snapshot(self, envs=None):
+        """The state of env ``envs[j]`` (default: every env) as a ``Snapshot`` of opaque records on
+        the GPU, everything the step kernels keep per env (the reference's counterpart is a copy
+        of the env object, fields SPaRC_Gym.py:141-187).  One launch, asynchronous."""
+        from .snapshot import Snapshot
+        self._stream()
+        info = self.core.snapshot_info()
+        idx = None if envs is None else self._index_arg(envs, "envs", self.num_envs)
+        M = self.num_envs if idx is None else int(idx.shape[0])
+        if M < 1:
+            raise ValueError("envs must not be empty")
+        rec = torch.empty((M, info.record_bytes), dtype=torch.uint8, device=self.device)
+        self.core.snapshot_device(None if idx is None else idx.data_ptr(), M, rec.data_ptr())
+        return Snapshot(rec, info)
+
+    def restore(self, snap, src=None, mask=None):
+        """Env ``i`` with ``mask[i]`` (default: all) takes record ``src[i]`` of ``snap`` (default:
+        record ``i``, which needs ``len(snap) == num_envs``).  Returns ``(obs, info)`` as
+        ``reset()``: ``info['legal_mask']`` [N] uint8 (0 for envs not restored),
+        ``info['restored']`` the bool mask.  ValueError naming the field when the snapshot's header
+        does not match this env (words, pitch, traceback, max_steps, record_bytes, table_hash);
+        ``autoreset`` may differ: pending envs of a snapshot then autoreset on their next step."""
+        from .snapshot import info_mismatch
+        self._stream()
+        bad = info_mismatch(snap.info, self.core.snapshot_info())
+        if bad is not None:
+            raise ValueError(f"snapshot does not match this env: {bad} differs")
+        M, n = len(snap), self.num_envs
+        if M < 1:
+            raise ValueError("empty snapshot")
+        if src is None and M != n:
+            raise ValueError(f"src is needed to restore {M} records into {n} envs")
+        idx = None if src is None else self._index_arg(src, "src", M)
+        if idx is not None and idx.shape != (n,):
+            raise ValueError(f"src must have shape ({n},)")
+        m = self._mask_arg(mask)
+        rec = snap.records
+        if not isinstance(rec, torch.Tensor):
+            rec = torch.from_numpy(np.ascontiguousarray(rec, np.uint8))
+        rec = rec.to(self.device).contiguous()
+        flags = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self.core.restore_device(snap.info, rec.data_ptr(), M, None if idx is None else idx.data_ptr(),
+                                 None if m is None else m.data_ptr(), flags.data_ptr())
+        return self._restored(flags, m)
+
+    def fork(self, src, mask=None):
+        """Env ``i`` with ``mask[i]`` (default: all) takes the state of env ``src[i]``, as one
+        simultaneous assignment (every read sees the state from before the call: permutations
+        and fan-out from one env are fine).  Returns ``(obs, info)`` as ``restore``."""
+        self._stream()
+        n = self.num_envs
+        idx = self._index_arg(src, "src", n)
+        if idx.shape != (n,):
+            raise ValueError(f"src must have shape ({n},)")
+        m = self._mask_arg(mask)
+        flags = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self.core.fork_device(idx.data_ptr(), None if m is None else m.data_ptr(), flags.data_ptr())
+        return self._restored(flags, m)
 
     def state(self):
         """Host snapshot of the per-env state (x, y, path_len, step, puzzle, outcome, visited bits)."""
