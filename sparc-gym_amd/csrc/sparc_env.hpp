@@ -27,9 +27,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sparc_layout.hpp"
+
 namespace sparc {
 
-constexpr uint32_t kNone = 0xFFFFu;
 constexpr uint32_t kErrPuzzle = 1, kErrTrie = 2;
 
 // trie record w2 fields

@@ -30,6 +30,8 @@
 #include "sparc_move1.hpp"
 #include "sparc_rules.hpp"
 #include "sparc_snapshot.hpp"
+#include "sparc_devbuf.hpp"
+#include "sparc_tables.hpp"
 #include "sparc_gym_amd.h"
 
 using namespace sparc;
@@ -47,7 +49,6 @@ __host__ __device__ constexpr size_t tiles_lds_bytes() { return (size_t)kWaves *
 // flag word per wave (the audit-pair join, k_rollout)
 template <int EPW>
 __host__ __device__ constexpr size_t bits_lds_bytes() { return (size_t)kWaves * 2 * EPW * kTile + 4 * kWaves; }
-constexpr size_t kMaxDynLds = 160 * 1024;   // one workgroup may own all 160 KiB (gfx950)
 
 // LDS bytes of the staged puzzle rows: (W = 1) compact row + reset board, or (W > 1) info +
 // root record + the open bitboard that the generic step reads every step
@@ -1395,7 +1396,6 @@ struct R1Geom {
     static constexpr size_t kSimple = kStk + (size_t)G * 64 * 64;          // [512] ring_simple (INC audits)
     static constexpr size_t kBase = kSimple + 512;                         // then the W = 1 puzzle rows
 };
-constexpr uint32_t kRingShift = 57;
 
 // INC: incremental audits (RegionSet1, sparc_rules.hpp): audit wave q takes the steps of the
 // q-th block of RT / A consecutive steps of each tile in order, keeping the env's regions from
@@ -1935,6 +1935,54 @@ struct AuditCall {
     int32_t* stats = nullptr;
 };
 
+// One loaded puzzle table: the device tables, the host arrays later calls read, and the facts the
+// launches select kernels by (sparc_tables.hpp HostPuzzleTables).  Built as a local by
+// sparc_load_puzzles and moved into the context only when every upload has succeeded.
+struct PuzzleDev {
+    uint32_t num_puzzles = 0, num_nodes = 0;
+    std::vector<uint4> h_info;         // host copy of t_info (the device rows)
+    DevBuf<uint64_t> open, init;
+    DevBuf<uint4> info, root, trie, row1;
+    DevBuf<uint2> trie8;               // split-kernel tables (empty: a puzzle's trie exceeds 15-bit nodes)
+    DevBuf<uint2> trieg;               // [nodes][4]: the record of each node's field-d node (k_rollout1s)
+    // mixed split tables (sparc_trie.hpp TrieLaneT<true>): 4-B records for tries of at most 127
+    // nodes, 8-B ones for the rest, byte-addressed, and their trie rows; taken by k_rollout1s on
+    // pools past the LDS row budget
+    DevBuf<uint8_t> trie4;
+    DevBuf<uint4> trow4;
+    bool mixed_pays = false;   // the 8-B records outgrow an XCD's L2 (build_puzzle_tables, sparc_reset_host)
+    std::vector<uint32_t> nodes8;   // W = 1: trie nodes (8-B records) per puzzle, for the XCD hot set
+    DevBuf<uint4> trow, mrow;
+    // multi-word split kernel (k_rolloutWs): move rows and reset boards; split_w false when the
+    // pool does not fit its layout (pitch > 15, LDS, or no trie8)
+    DevBuf<uint4> mroww;
+    DevBuf<uint32_t> boardw;
+    SplitGeom sgeom{};
+    bool split_w = false;
+    bool ring_ok = false;     // W = 1 and every board fits below kRingShift (k_rollout1r's ring word)
+    uint64_t table_hash = 0;  // identity of the table for snapshots (sparc_snapshot_info)
+};
+
+// One loaded rule table (sparc_tables.hpp HostRuleTables), built and committed like PuzzleDev.
+struct RuleDev {
+    DevBuf<uint64_t> planes;        // [P][RP_COUNT][W] (sparc_layout.hpp: the ABI planes + derived ones)
+    bool area = false;
+    DevBuf<uint2> inst_fc;          // [P] {first, count | kHostFit} (sparc_rules.hpp RulesTab)
+    DevBuf<uint32_t> inst;
+    DevBuf<uint2> shape_range;      // [S] {first offset, count}
+    DevBuf<int32_t> shape_area;
+    DevBuf<int8_t> shape_off;
+    DevBuf<uint32_t> reg_off, reg_tab;   // region-code table (sparc_rules.hpp)
+    DevBuf<uint64_t> rows;          // the audit's per-puzzle rows (RulesTab::rows)
+    bool tab_all = false;           // every puzzle has a region-code table (k_rollout1r's audit)
+    // exact-fit searches past the GPU's node cap (sparc_set_fit_cap) are finished on the host
+    // from these copies of the rule table (sparc_rules.hpp exact_fit, the same code)
+    std::vector<uint32_t> h_inst;
+    std::vector<uint2> h_inst_fc, h_shape_range;
+    std::vector<int8_t> h_shape_off;
+    size_t host_fit_puzzles = 0;    // puzzles flagged kHostFit
+};
+
 struct Ctx {
     sparc_config cfg{};
     int device = 0;
@@ -1942,91 +1990,47 @@ struct Ctx {
     uint32_t n = 0;
     int W = 1;
     bool loaded = false, has_state = false;
-    uint32_t num_puzzles = 0, num_nodes = 0;
-    std::vector<uint32_t> h_info;      // host copy of the loaded table's info rows [P][4]
-    // device buffers
-    uint64_t *vis = nullptr, *dirs = nullptr;
-    uint32_t *pos = nullptr, *aux = nullptr, *step = nullptr, *pid = nullptr;
-    uint64_t* t_open = nullptr;
-    uint4 *t_info = nullptr, *t_root = nullptr, *t_trie = nullptr;
-    uint64_t* t_init = nullptr;
-    uint4* t_row1 = nullptr;
-    uint2* t_trie8 = nullptr;          // split-kernel tables (null: a puzzle's trie exceeds 15-bit nodes)
-    uint2* t_trieg = nullptr;          // [nodes][4]: the record of each node's field-d node (k_rollout1s)
-    // mixed split tables (sparc_trie.hpp TrieLaneT<true>): 4-B records for tries of at most 127
-    // nodes, 8-B ones for the rest, byte-addressed, and their trie rows; taken by k_rollout1s on
-    // pools past the LDS row budget
-    uint8_t* t_trie4 = nullptr;
-    uint4* t_trow4 = nullptr;
-    bool mixed_pays = false;   // the 8-B records outgrow an XCD's L2 (sparc_load_puzzles, sparc_reset_host)
-    std::vector<uint32_t> nodes8;   // W = 1: trie nodes (8-B records) per puzzle, for the XCD hot set
+    PuzzleDev pz;                      // the loaded puzzle table (sparc_load_puzzles)
+    // env state (SoA) and the staging buffers of the host-pointer calls
+    DevBuf<uint64_t> vis, dirs;
+    DevBuf<uint32_t> pos, aux, step, pid;
+    DevBuf<int32_t> err;
+    DevBuf<uint8_t> s_act, s_flags, s_mask;
+    DevBuf<int8_t> s_rew;
+    DevBuf<uint32_t> s_pidx;
     int mixed_trie = 0;        // SPARC_VARIANT_MIXED_TRIE: 0 when it pays, 1 always, 2 never
-    uint4 *t_trow = nullptr, *t_mrow = nullptr;
-    // multi-word split kernel (k_rolloutWs): move rows and reset boards; split_w false when the
-    // pool does not fit its layout (pitch > 15, LDS, or no trie8)
-    uint4* t_mroww = nullptr;
-    uint32_t* t_boardw = nullptr;
-    SplitGeom sgeom{};
-    bool split_w = false;
-    int32_t* err = nullptr;
-    uint8_t *s_act = nullptr, *s_flags = nullptr, *s_mask = nullptr;
-    int8_t* s_rew = nullptr;
-    uint32_t* s_pidx = nullptr;
-    // rule table (sparc_load_rules)
     bool rules = false;
-    uint64_t* r_planes = nullptr;   // [P][RP_COUNT][W] (sparc_rules.hpp: the ABI planes + derived ones)
-    bool r_area = false;
-    uint2* r_inst_fc = nullptr;     // [P] {first, count | kHostFit} (sparc_rules.hpp RulesTab)
-    uint32_t* r_inst = nullptr;
-    uint2* r_shape_range = nullptr;  // [S] {first offset, count}
-    int32_t* r_shape_area = nullptr;
-    int8_t* r_shape_off = nullptr;
-    FitMemo<kMemo>* r_memo = nullptr;   // [N] per-env exact-fit memo of the audit (zeroed at sparc_load_rules)
-    uint32_t *r_reg_off = nullptr, *r_reg_tab = nullptr;   // region-code table (sparc_rules.hpp)
-    uint64_t* r_rows = nullptr;   // the audit's per-puzzle rows (RulesTab::rows)
-    bool r_tab_all = false;   // every puzzle has a region-code table (k_rollout1r's audit)
-    bool ring_ok = false;     // W = 1 and every board fits below kRingShift (k_rollout1r's ring word)
+    RuleDev rl;                        // the loaded rule table (sparc_load_rules)
+    DevBuf<FitMemo<kMemo>> r_memo;     // [N] per-env exact-fit memo of the audit (zeroed at sparc_load_rules)
     // kernel variants with identical results, set only by sparc_set_variant (A/B runs, tests)
     bool rules_generic = false;   // rule rollouts on k_rollout<..., RULES>
     bool io_codes_off = false;    // k_rollout1s / k_rolloutWs keep the reward codes on the trie wave
     int r1r_shape = 0;            // k_rollout1r's <G, A, RT> (0: <2, 5, 15>; 1-5: A/B, tests)
     bool obs_inline = false;      // 'new'-plane rollouts on k_rollout<..., OBS> instead of k_rollout_obsw
-    // exact-fit searches past the GPU's node cap (sparc_set_fit_cap) are finished on the host
-    // from these copies of the rule table (sparc_rules.hpp exact_fit, the same code)
     uint32_t fit_cap = kFitCap;
     size_t reg_entries = (size_t)1 << 28;   // region-code table budget (entries of 4 bits)
-    std::vector<uint32_t> h_inst;
-    std::vector<uint2> h_inst_fc, h_shape_range;
-    size_t host_fit_puzzles = 0;    // puzzles flagged kHostFit by the last sparc_load_rules
-    std::vector<int8_t> h_shape_off;
-    unsigned long long* fq_count = nullptr;   // FitQueue of the audits (sparc_rules_finish)
-    FitTodo* fq_items = nullptr;
-    uint64_t fq_cap = 0;            // its capacity (grown by sparc_rules_finish on overflow)
+    DevBuf<unsigned long long> fq_count;   // FitQueue of the audits (sparc_rules_finish)
+    DevBuf<FitTodo> fq_items;       // its size is the queue's capacity (grown by sparc_rules_finish on overflow)
     uint64_t fq_last = 0, fq_reruns = 0;   // searches the last finish ran; calls run again
-    uint64_t* h_count = nullptr;    // pinned host word the queue count is read into
+    PinnedWord<uint64_t> h_count;   // pinned host word the queue count is read into
     // answers of the host's exact fits (sparc_rules.hpp HostFits), so that later audits look them
     // up instead of queueing the same search again: host mirror + device copy
     std::vector<uint4> h_hf;
-    uint4* d_hf = nullptr;
+    DevBuf<uint4> d_hf;
     uint32_t hf_used = 0;
     bool hostfits_off = false;    // SPARC_VARIANT_HOST_FITS = 1: answers not kept (tests: the queue path)
     // the one-env record of sparc_env_step / _reset / _read (pinned, written by the kernels)
-    sparc_env_record* h_rec = nullptr;
-    sparc_env_record* d_rec = nullptr;
+    PinnedWord<sparc_env_record> h_rec;
     AuditCall last_audit;           // the last queueing audit call (sparc_rules_finish)
     // the state a generic rule rollout started from (re-run on a queue overflow)
-    void* snap = nullptr;
-    size_t snap_bytes = 0;
-    // snapshot / restore / fork (sparc_snapshot.hpp): hash of the loaded table's host arrays, and
-    // scratch that grows on demand: records (fork, the *_host forms) and an index list
-    uint64_t table_hash = 0;
-    void* fk_rec = nullptr;
-    size_t fk_rec_bytes = 0;
-    uint32_t* fk_idx = nullptr;
-    size_t fk_idx_bytes = 0;
-    uint16_t* s_bits = nullptr;
-    uint8_t* s_region = nullptr;
-    uint64_t* s_fit = nullptr;
+    DevBuf<uint8_t> snap;
+    // snapshot / restore / fork (sparc_snapshot.hpp): scratch that grows on demand: records
+    // (fork, the *_host forms) and an index list
+    DevBuf<uint8_t> fk_rec;
+    DevBuf<uint32_t> fk_idx;
+    DevBuf<uint16_t> s_bits;        // per-env audit outputs of the host-pointer / one-env calls
+    DevBuf<uint8_t> s_region;
+    DevBuf<uint64_t> s_fit;
     std::string msg;
 };
 
@@ -2061,31 +2065,33 @@ struct DevGuard {
     DevGuard& operator=(const DevGuard&) = delete;
 };
 
-Params make_params(const Ctx* c) {
+// make_params and rules_tab are the only places that turn buffers into the raw-pointer structs
+// the kernels take
+Params make_params(const Ctx* c, const PuzzleDev& z) {
     Params p{};
-    p.tab.open = c->t_open;
-    p.tab.info = c->t_info;
-    p.tab.root = c->t_root;
-    p.tab.trie = c->t_trie;
-    p.tab.init = c->t_init;
-    p.tab.row1 = c->t_row1;
-    p.tab.trie8 = c->t_trie8;
-    p.tab.trieg = c->t_trieg;
-    p.tab.trow = c->t_trow;
-    p.tab.mrow = c->t_mrow;
-    p.tab.num_puzzles = c->num_puzzles;
-    p.st.vis = c->vis;
-    p.st.dirs = c->dirs;
-    p.st.pos = c->pos;
-    p.st.aux = c->aux;
-    p.st.step = c->step;
-    p.st.pid = c->pid;
+    p.tab.open = z.open.get();
+    p.tab.info = z.info.get();
+    p.tab.root = z.root.get();
+    p.tab.trie = z.trie.get();
+    p.tab.init = z.init.get();
+    p.tab.row1 = z.row1.get();
+    p.tab.trie8 = z.trie8.get();
+    p.tab.trieg = z.trieg.get();
+    p.tab.trow = z.trow.get();
+    p.tab.mrow = z.mrow.get();
+    p.tab.num_puzzles = z.num_puzzles;
+    p.st.vis = c->vis.get();
+    p.st.dirs = c->dirs.get();
+    p.st.pos = c->pos.get();
+    p.st.aux = c->aux.get();
+    p.st.step = c->step.get();
+    p.st.pid = c->pid.get();
     p.n = c->n;
     p.pitch = (uint32_t)c->cfg.pitch;
     p.max_steps = c->cfg.max_steps;
     p.autoreset = c->cfg.autoreset;
     p.env_offset = (uint64_t)c->cfg.env_offset;
-    p.err = c->err;
+    p.err = c->err.get();
     const uint32_t P = p.pitch;
     p.nbr_pos = (2u * P) | ((P - 1u) << 8) | (0u << 16) | ((P + 1u) << 24);
     if (c->W == 1 && split1_pitch_ok(P)) {
@@ -2094,6 +2100,7 @@ Params make_params(const Ctx* c) {
     }
     return p;
 }
+Params make_params(const Ctx* c) { return make_params(c, c->pz); }
 
 inline dim3 grid_for(size_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
@@ -2141,31 +2148,27 @@ struct R1Shape {
 };
 
 constexpr uint64_t kFitQueueCap = 1u << 16;   // exact fits past the node cap per audit call (grown)
-constexpr size_t kMixedTrieBytes = (size_t)4 << 20;   // an XCD's L2: past it the mixed trie tables pay
-// puzzles an env plays per 2,000-step launch under random actions (episodes of ~300 steps, next
-// puzzle on each autoreset): the window of its start puzzle that xcd_hot_bytes counts
-constexpr uint32_t kHotWalk = 8;
 constexpr uint64_t kFitQueueMax = (uint64_t)1 << 28;   // 6 GB of FitTodo
 
 // the loaded rule table as the kernels take it; queue: push searches past the node cap to the
 // FitQueue (audits), or not (the region-code table build: the host scans the table instead)
-RulesTab rules_tab(const Ctx* c, bool queue) {
+RulesTab rules_tab(const Ctx* c, const RuleDev& r, bool queue) {
     RulesTab rt{};
-    rt.planes = c->r_planes;
-    rt.inst_fc = c->r_inst_fc;
-    rt.inst = c->r_inst;
-    rt.shape_range = c->r_shape_range;
-    rt.shape_area = c->r_shape_area;
-    rt.shape_off = c->r_shape_off;
-    rt.num_puzzles = c->num_puzzles;
-    rt.area = c->r_area ? 1u : 0u;
+    rt.planes = r.planes.get();
+    rt.inst_fc = r.inst_fc.get();
+    rt.inst = r.inst.get();
+    rt.shape_range = r.shape_range.get();
+    rt.shape_area = r.shape_area.get();
+    rt.shape_off = r.shape_off.get();
+    rt.num_puzzles = c->pz.num_puzzles;
+    rt.area = r.area ? 1u : 0u;
     rt.fit_cap = c->fit_cap;
-    rt.reg_off = c->r_reg_off;
-    rt.reg_tab = c->r_reg_tab;
-    rt.fq = FitQueue{queue ? c->fq_count : nullptr, c->fq_items, c->fq_cap};
+    rt.reg_off = r.reg_off.get();
+    rt.reg_tab = r.reg_tab.get();
+    rt.fq = FitQueue{queue ? c->fq_count.get() : nullptr, c->fq_items.get(), c->fq_items.size()};
     rt.hf = c->hostfits_off ? HostFits{nullptr, 0u, 0u}
-                            : HostFits{c->d_hf, c->h_hf.empty() ? 0u : (uint32_t)c->h_hf.size() - 1u, c->d_hf ? c->hf_used : 0u};
-    rt.rows = c->r_rows;
+                            : HostFits{c->d_hf.get(), c->h_hf.empty() ? 0u : (uint32_t)c->h_hf.size() - 1u, c->d_hf ? c->hf_used : 0u};
+    rt.rows = r.rows.get();
     return rt;
 }
 
@@ -2173,13 +2176,13 @@ RulesTab rules_tab(const Ctx* c, bool queue) {
 // HOST, without a node cap (the reference's search is unbounded): exact_fit of sparc_rules.hpp,
 // the code the GPU runs, over the host copies of the rule table.  1 fits, 0 does not.
 template <int W>
-int host_fit_w(const Ctx* c, uint32_t q, uint64_t rm) {
-    const uint32_t w0 = c->h_info[4 * (size_t)q], X = w0 & 0xFFu, Y = (w0 >> 8) & 0xFFu;
+int host_fit_w(const Ctx* c, const RuleDev& r, uint32_t q, uint64_t rm) {
+    const uint32_t w0 = c->pz.h_info[q].x, X = w0 & 0xFFu, Y = (w0 >> 8) & 0xFFu;
     RulesTab rt{};
-    rt.inst = c->h_inst.data();
-    rt.shape_range = c->h_shape_range.data();
-    rt.shape_off = c->h_shape_off.data();
-    const uint2 fc = c->h_inst_fc[q];
+    rt.inst = r.h_inst.data();
+    rt.shape_range = r.h_shape_range.data();
+    rt.shape_off = r.h_shape_off.data();
+    const uint2 fc = r.h_inst_fc[q];
     const FitIn fin = fit_in(rt, fc.x, fc.y & ~kHostFit, X, Y);
     const uint32_t P = (uint32_t)c->cfg.pitch;
     BB<W> Rc = BB<W>::zero();
@@ -2189,8 +2192,8 @@ int host_fit_w(const Ctx* c, uint32_t q, uint64_t rm) {
     if (fc.y & kHostFit) return exact_fit<W, uint64_t, kHostFitMax, kHostFitMax, kHostFitPlanes>(fin, Rc, rm, ~0ull);
     return exact_fit<W, uint64_t>(fin, Rc, rm, ~0ull);
 }
-int host_fit(const Ctx* c, uint32_t q, uint64_t rm) {
-    return c->W == 1 ? host_fit_w<1>(c, q, rm) : c->W == 2 ? host_fit_w<2>(c, q, rm) : host_fit_w<4>(c, q, rm);
+int host_fit(const Ctx* c, const RuleDev& r, uint32_t q, uint64_t rm) {
+    return c->W == 1 ? host_fit_w<1>(c, r, q, rm) : c->W == 2 ? host_fit_w<2>(c, r, q, rm) : host_fit_w<4>(c, r, q, rm);
 }
 
 // fn(k) for k in [0, n) on up to 16 host threads (the host's exact-fit searches)
@@ -2246,18 +2249,13 @@ int sparc_create(int device, const sparc_config* cfg, void** ctx_out) {
     if (hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking) != hipSuccess)
         return cleanup(fail(nullptr, SPARC_E_HIP, "hipStreamCreate failed"));
     c->stream = c->own;
-    bool ok = hipMalloc(&c->vis, sizeof(uint64_t) * n * c->W) == hipSuccess &&
-              hipMalloc(&c->pos, sizeof(uint32_t) * n) == hipSuccess &&
-              hipMalloc(&c->aux, sizeof(uint32_t) * n) == hipSuccess &&
-              hipMalloc(&c->step, sizeof(uint32_t) * n) == hipSuccess &&
-              hipMalloc(&c->pid, sizeof(uint32_t) * n) == hipSuccess &&
-              hipMalloc(&c->err, sizeof(int32_t)) == hipSuccess &&
-              hipMalloc(&c->s_act, n) == hipSuccess && hipMalloc(&c->s_flags, n) == hipSuccess &&
-              hipMalloc(&c->s_mask, n) == hipSuccess && hipMalloc(&c->s_rew, n) == hipSuccess &&
-              hipMalloc(&c->s_pidx, sizeof(uint32_t) * n) == hipSuccess;
-    if (ok && cfg->traceback) ok = hipMalloc(&c->dirs, sizeof(uint64_t) * n * 2 * c->W) == hipSuccess;
+    bool ok = c->vis.alloc(n * c->W) == hipSuccess && c->pos.alloc(n) == hipSuccess && c->aux.alloc(n) == hipSuccess &&
+              c->step.alloc(n) == hipSuccess && c->pid.alloc(n) == hipSuccess && c->err.alloc(1) == hipSuccess &&
+              c->s_act.alloc(n) == hipSuccess && c->s_flags.alloc(n) == hipSuccess &&
+              c->s_mask.alloc(n) == hipSuccess && c->s_rew.alloc(n) == hipSuccess && c->s_pidx.alloc(n) == hipSuccess;
+    if (ok && cfg->traceback) ok = c->dirs.alloc(n * 2 * c->W) == hipSuccess;
     if (!ok) return cleanup(fail(nullptr, SPARC_E_NOMEM, "hipMalloc failed for the env state"));
-    if (hipMemset(c->err, 0, sizeof(int32_t)) != hipSuccess)
+    if (hipMemset(c->err.get(), 0, sizeof(int32_t)) != hipSuccess)
         return cleanup(fail(nullptr, SPARC_E_HIP, "hipMemset failed"));
     *ctx_out = c;
     return SPARC_OK;
@@ -2269,19 +2267,9 @@ int sparc_destroy(void* ctx) {
     if (!c) return SPARC_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void* bufs[] = {c->vis, c->dirs, c->pos, c->aux, c->step, c->pid, c->t_open, c->t_info, c->t_root, c->t_trie, c->t_init, c->t_row1,
-                    c->t_trie8, c->t_trow, c->t_mrow, c->t_mroww, c->t_boardw, c->err, c->s_act, c->s_flags, c->s_mask, c->s_rew, c->s_pidx, c->r_planes, c->r_inst_fc,
-                    c->r_inst, c->r_shape_range, c->r_shape_area, c->r_shape_off, c->r_memo, c->s_bits, c->s_region, c->s_fit, c->r_reg_off, c->r_reg_tab, c->fq_count, c->fq_items, c->r_rows,
-                    c->t_trieg, c->d_hf, c->t_trie4, c->t_trow4};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (c->snap) (void)hipFree(c->snap);
-    if (c->fk_rec) (void)hipFree(c->fk_rec);
-    if (c->fk_idx) (void)hipFree(c->fk_idx);
-    if (c->h_count) (void)hipHostFree(c->h_count);
-    if (c->h_rec) (void)hipHostFree(c->h_rec);
-    if (c->own) (void)hipStreamDestroy(c->own);
-    delete c;
+    const hipStream_t own = c->own;
+    delete c;   // releases every buffer
+    if (own) (void)hipStreamDestroy(own);
     return SPARC_OK;
 }
 
@@ -2308,9 +2296,9 @@ int sparc_sync(void* ctx) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int32_t e = 0;
-    HIPCHK(c, hipMemcpy(&e, c->err, sizeof(e), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&e, c->err.get(), sizeof(e), hipMemcpyDeviceToHost));
     if (e) {
-        HIPCHK(c, hipMemset(c->err, 0, sizeof(int32_t)));
+        HIPCHK(c, hipMemset(c->err.get(), 0, sizeof(int32_t)));
         if (e & 2) return fail(c, SPARC_E_STATE, "device-side trie node out of range (state corrupted)");
         if (e & 8) return fail(c, SPARC_E_STATE, "rule audit: env puzzle index outside the rule table");
         if (e & kErrJoin) return fail(c, SPARC_E_STATE, "rule rollout: an audit wave pair did not join (outputs unreliable)");
@@ -2321,352 +2309,54 @@ int sparc_sync(void* ctx) {
     return SPARC_OK;
 }
 
+// Validate and build on the host (sparc_tables.hpp), upload into a local PuzzleDev, and commit it
+// to the context only after the last upload: a call that fails, for whatever reason, leaves the
+// context and its loaded table exactly as they were.
 int sparc_load_puzzles(void* ctx, const sparc_puzzle_table* t) {
     DevGuard dg;
     Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c || !t || !t->open || !t->info) return fail(c, SPARC_E_INVALID, "null argument");
-    if (t->num_puzzles < 1) return fail(c, SPARC_E_INVALID, "empty puzzle table");
-    if (t->num_nodes < 0 || (t->num_nodes > 0 && !t->trie)) return fail(c, SPARC_E_INVALID, "bad trie");
-    const int W = c->W;
-    const uint32_t pitch = (uint32_t)c->cfg.pitch;
-    // validate every index the kernels will follow, so no launch can read out of bounds
-    for (int q = 0; q < t->num_puzzles; ++q) {
-        const uint32_t* inf = t->info + 4 * (size_t)q;
-        const uint32_t X = inf[0] & 0xFF, Y = (inf[0] >> 8) & 0xFF;
-        const uint32_t sx = (inf[0] >> 16) & 0xFF, sy = inf[0] >> 24;
-        const uint32_t tx = inf[1] & 0xFF, ty = (inf[1] >> 8) & 0xFF, fl = inf[1] >> 16;
-        const uint32_t base = inf[2], cnt = inf[3];
-        char m[160];
-        const bool fits = W == 1 ? (Y < pitch && pitch <= 15 && (X + 1) * pitch <= 64u)
-                                 : (Y <= pitch && (X - 1) * pitch + Y <= 64u * W);
-        if (X < 1 || Y < 1 || !fits) {
-            snprintf(m, sizeof m, "puzzle %d: lattice %ux%u does not fit pitch %u / %d words%s", q, X, Y, pitch, W,
-                     W == 1 ? " (words=1 needs the padded layout)" : "");
-            return fail(c, SPARC_E_INVALID, m);
-        }
-        if (sx >= X || sy >= Y || tx >= X || ty >= Y) {
-            snprintf(m, sizeof m, "puzzle %d: start/target outside the lattice", q);
-            return fail(c, SPARC_E_INVALID, m);
-        }
-        if ((fl & 2u) && (cnt == 0 || (uint64_t)base + cnt > (uint64_t)t->num_nodes || cnt > (W == 1 ? 0x7FFFu : 0xFFFFu))) {
-            snprintf(m, sizeof m, "puzzle %d: trie range out of bounds", q);
-            return fail(c, SPARC_E_INVALID, m);
-        }
-        if (fl & 2u) {
-            for (uint32_t k = 0; k < cnt; ++k) {
-                const uint32_t* r = t->trie + 4 * ((size_t)base + k);
-                const uint32_t ch[4] = {r[0] & 0xFFFF, r[0] >> 16, r[1] & 0xFFFF, r[1] >> 16};
-                for (uint32_t v : ch)
-                    if (v != kNone && v >= cnt) return fail(c, SPARC_E_INVALID, "trie child out of range");
-                const uint32_t par = r[2] & 0xFFFF;
-                if (k > 0 && par >= cnt) return fail(c, SPARC_E_INVALID, "trie parent out of range");
-            }
-        }
-    }
+    if (!c) return fail(c, SPARC_E_INVALID, "null argument");
+    HostPuzzleTables h;
+    if (const BuildError e = build_puzzle_tables(t, c->W, (uint32_t)c->cfg.pitch, c->cfg.traceback != 0,
+                                                 SplitLds{(uint32_t)kW_Board, splitw_fin_bytes()}, h))
+        return fail(c, e.code, e.msg);
     HIPCHK(c, hipSetDevice(c->device));
+    PuzzleDev d;
+    const size_t P = h.num_puzzles;
+    const uint4 no_trie = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);   // a table without nodes
+    HIPCHK(c, upload(d.open, t->open, P * c->W));
+    HIPCHK(c, upload(d.trie, t->num_nodes > 0 ? reinterpret_cast<const uint4*>(t->trie) : &no_trie,
+                     (size_t)std::max(t->num_nodes, 1)));
+    HIPCHK(c, upload(d.info, h.info));
+    HIPCHK(c, upload(d.root, h.root));
+    HIPCHK(c, upload(d.init, h.init));
+    HIPCHK(c, upload(d.row1, h.row1));
+    if (h.small) {
+        HIPCHK(c, upload(d.trie8, h.trie8));
+        HIPCHK(c, upload(d.trieg, h.trieg));
+        HIPCHK(c, upload(d.trow, h.trow));
+        HIPCHK(c, upload(d.mrow, h.mrow));
+    }
+    if (!h.trie4.empty()) {
+        HIPCHK(c, upload(d.trie4, h.trie4));
+        HIPCHK(c, upload(d.trow4, h.trow4));
+    }
+    if (h.split_w) {
+        HIPCHK(c, upload(d.mroww, h.mroww));
+        HIPCHK(c, upload(d.boardw, h.boardw));
+    }
+    d.num_puzzles = h.num_puzzles;
+    d.num_nodes = h.num_nodes;
+    d.h_info = std::move(h.info);
+    d.mixed_pays = h.mixed_pays;
+    d.nodes8 = std::move(h.nodes8);
+    d.sgeom = h.sgeom;
+    d.split_w = h.split_w;
+    d.ring_ok = h.ring_ok;
+    d.table_hash = h.table_hash;
+    // no launch still reads the old tables once the stream has drained; then swap
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->t_open) HIPCHK(c, hipFree(c->t_open));
-    if (c->t_info) HIPCHK(c, hipFree(c->t_info));
-    if (c->t_trie) HIPCHK(c, hipFree(c->t_trie));
-    if (c->t_root) HIPCHK(c, hipFree(c->t_root));
-    if (c->t_init) HIPCHK(c, hipFree(c->t_init));
-    if (c->t_row1) HIPCHK(c, hipFree(c->t_row1));
-    if (c->t_trie8) HIPCHK(c, hipFree(c->t_trie8));
-    if (c->t_trieg) HIPCHK(c, hipFree(c->t_trieg));
-    if (c->t_trie4) HIPCHK(c, hipFree(c->t_trie4));
-    if (c->t_trow4) HIPCHK(c, hipFree(c->t_trow4));
-    c->t_trie4 = nullptr;
-    c->t_trow4 = nullptr;
-    c->mixed_pays = false;
-    c->nodes8.clear();
-    if (c->t_trow) HIPCHK(c, hipFree(c->t_trow));
-    if (c->t_mrow) HIPCHK(c, hipFree(c->t_mrow));
-    if (c->t_mroww) HIPCHK(c, hipFree(c->t_mroww));
-    if (c->t_boardw) HIPCHK(c, hipFree(c->t_boardw));
-    c->t_mroww = nullptr;
-    c->t_boardw = nullptr;
-    c->split_w = false;
-    c->t_trie8 = nullptr;
-    c->t_trieg = nullptr;
-    c->t_trow = nullptr;
-    c->t_mrow = nullptr;
-    c->t_init = nullptr;
-    c->t_row1 = nullptr;
-    c->t_open = nullptr;
-    c->t_info = nullptr;
-    c->t_root = nullptr;
-    c->t_trie = nullptr;
-    const size_t P = (size_t)t->num_puzzles, nn = (size_t)(t->num_nodes > 0 ? t->num_nodes : 1);
-    HIPCHK(c, hipMalloc(&c->t_open, sizeof(uint64_t) * P * W));
-    HIPCHK(c, hipMalloc(&c->t_info, sizeof(uint4) * P));
-    HIPCHK(c, hipMalloc(&c->t_trie, sizeof(uint4) * nn));
-    HIPCHK(c, hipMalloc(&c->t_root, sizeof(uint4) * P));
-    // each puzzle's root record, so that a reset needs no dependent trie load
-    std::vector<uint4> roots(P, make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, kNone, 0u));
-    for (size_t q = 0; q < P; ++q) {
-        const uint32_t* inf = t->info + 4 * q;
-        if ((inf[1] >> 16) & 2u) {
-            const uint32_t* r = t->trie + 4 * (size_t)inf[2];
-            roots[q] = make_uint4(r[0], r[1], r[2], r[3]);
-        }
-    }
-    HIPCHK(c, hipMemcpy(c->t_root, roots.data(), sizeof(uint4) * P, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->t_open, t->open, sizeof(uint64_t) * P * W, hipMemcpyHostToDevice));
-    // device copy of info: w3 = trie node count | legal mask of the reset state << 16, and for
-    // the padded W = 1 layout the compact rows and the free board at reset
-    std::vector<uint4> dinfo(P);
-    std::vector<uint64_t> init(P, 0);
-    std::vector<uint4> row1(P, make_uint4(0u, 0u, 0u, 0u));
-    for (size_t q = 0; q < P; ++q) {
-        const uint32_t* inf = t->info + 4 * q;
-        const uint32_t X = inf[0] & 0xFF, Y = (inf[0] >> 8) & 0xFF;
-        const uint32_t sx = (inf[0] >> 16) & 0xFF, sy = inf[0] >> 24;
-        auto open_at = [&](uint32_t x, uint32_t y) {
-            const uint32_t b = x * pitch + y;
-            return (t->open[q * W + (b >> 6)] >> (b & 63)) & 1ull;
-        };
-        uint32_t legal0 = 0;
-        const int dx[4] = {1, 0, -1, 0}, dy[4] = {0, -1, 0, 1};
-        for (int d = 0; d < 4; ++d) {
-            const int nx = (int)sx + dx[d], ny = (int)sy + dy[d];
-            if (nx >= 0 && ny >= 0 && nx < (int)X && ny < (int)Y && open_at(nx, ny)) legal0 |= 1u << d;
-        }
-        const uint32_t root_term = ((inf[1] >> 16) & 2u) ? ((roots[q].z >> 16) & 1u) : 0u;
-        dinfo[q] = make_uint4(inf[0], (inf[1] & 0x0007FFFFu) | (root_term << 19), inf[2],
-                              (inf[3] & 0xFFFFu) | (legal0 << 16));
-        if (W == 1) {
-            const uint32_t tx = inf[1] & 0xFF, ty = (inf[1] >> 8) & 0xFF;
-            // free board at reset, one row up (Env<1>): open points except the start
-            init[q] = (t->open[q] & ~(1ull << (sx * pitch + sy))) << pitch;
-            const uint32_t cnt = inf[3] & 0xFFFFu;
-            row1[q] = make_uint4((sx * pitch + sy) | ((tx * pitch + ty) << 8) | (dinfo[q].y & 0xFFFF0000u),
-                                 inf[2], (cnt ? cnt - 1u : 0u) | (legal0 << 16), 0u);
-        }
-    }
-    HIPCHK(c, hipMalloc(&c->t_row1, sizeof(uint4) * P));
-    HIPCHK(c, hipMemcpy(c->t_row1, row1.data(), sizeof(uint4) * P, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&c->t_init, sizeof(uint64_t) * P));
-    HIPCHK(c, hipMemcpy(c->t_info, dinfo.data(), sizeof(uint4) * P, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->t_init, init.data(), sizeof(uint64_t) * P, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemset(c->t_trie, 0xFF, sizeof(uint4) * nn));
-    if (t->num_nodes > 0)
-        HIPCHK(c, hipMemcpy(c->t_trie, t->trie, sizeof(uint4) * (size_t)t->num_nodes, hipMemcpyHostToDevice));
-    // split-kernel tables (sparc_trie.hpp): 8-B records, field d = the child in direction d,
-    // and the parent in the field of the direction back to it (the reverse of the move that
-    // reached the node: no reachable child lives there, as that point is on the path); per
-    // puzzle the trie row (root children, base, max node, flags) and, for W = 1, the move row
-    bool small = true;
-    for (size_t q = 0; q < P; ++q)
-        if (((t->info[4 * q + 1] >> 16) & 2u) && (t->info[4 * q + 3] & 0xFFFFu) > 0x7FFFu) small = false;
-    if (small) {
-        // each puzzle's records start on a 128-B line (16 records; rootless puzzles: base 0): in
-        // breadth-first order the root and the nodes near it, which most walks never leave,
-        // share ONE line per puzzle instead of straddling two, so pools whose tries outgrow an
-        // XCD's L2 refill fewer lines (the relative node indices, and so the env state, are
-        // unchanged; only the split tables move)
-        std::vector<size_t> b8(P, 0);
-        size_t nn8 = 0;
-        for (size_t q = 0; q < P; ++q) {
-            const uint32_t* inf = t->info + 4 * q;
-            if (!((inf[1] >> 16) & 2u)) continue;
-            nn8 = (nn8 + 15u) & ~(size_t)15u;
-            b8[q] = nn8;
-            nn8 += inf[3] & 0xFFFFu;
-        }
-        nn8 = std::max<size_t>(nn8, 1);
-        if (W == 1) {   // Env<1> (k_step, k_rollout1) reads trie8 at row1.y too
-            for (size_t q = 0; q < P; ++q) row1[q].y = (uint32_t)b8[q];
-            HIPCHK(c, hipMemcpy(c->t_row1, row1.data(), sizeof(uint4) * P, hipMemcpyHostToDevice));
-        }
-        std::vector<uint2> t8(nn8, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
-        auto packed = [&](size_t base, uint32_t k) {   // node k of a puzzle as index | terminal << 15
-            return k | (((t->trie[4 * (base + k) + 2] >> 16) & 1u) << 15);
-        };
-        for (size_t q = 0; q < P; ++q) {
-            const uint32_t* inf = t->info + 4 * q;
-            if (!((inf[1] >> 16) & 2u)) continue;
-            const size_t base = inf[2], bq = b8[q];
-            const uint32_t cnt = inf[3] & 0xFFFFu;
-            for (uint32_t k = 0; k < cnt; ++k) {
-                const uint32_t* r = t->trie + 4 * (base + k);
-                const uint32_t ch[4] = {r[0] & 0xFFFFu, r[0] >> 16, r[1] & 0xFFFFu, r[1] >> 16};
-                uint32_t f[4];
-                for (int d = 0; d < 4; ++d) f[d] = ch[d] == kNone ? 0xFFFFu : packed(base, ch[d]);
-                t8[bq + k] = make_uint2(f[0] | (f[1] << 16), f[2] | (f[3] << 16));
-            }
-            for (uint32_t k = 0; k < cnt; ++k) {           // parents, after every child field
-                const uint32_t* r = t->trie + 4 * (base + k);
-                const uint32_t ch[4] = {r[0] & 0xFFFFu, r[0] >> 16, r[1] & 0xFFFFu, r[1] >> 16};
-                for (uint32_t d = 0; d < 4; ++d) {
-                    if (ch[d] == kNone) continue;
-                    uint2& cr = t8[bq + ch[d]];
-                    const uint32_t back = d ^ 2u, sh = (back & 1u) * 16u;
-                    uint32_t& w = back < 2 ? cr.x : cr.y;
-                    w = (w & ~(0xFFFFu << sh)) | (packed(base, k) << sh);
-                }
-            }
-        }
-        std::vector<uint4> trow(P), mrow(P, make_uint4(0u, 0u, 0u, 0u));
-        for (size_t q = 0; q < P; ++q) {
-            const uint32_t* inf = t->info + 4 * q;
-            const uint32_t fl = (dinfo[q].y >> 16) & 0xFFFFu;
-            const uint32_t cnt = inf[3] & 0xFFFFu;
-            const uint2 rr = (fl & 2u) ? t8[b8[q]] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-            // flags as row1: bit0 solutions, bit1 root valid, bit3 root terminal
-            const uint32_t tf = (fl & 3u) | (((dinfo[q].y >> 19) & 1u) << 3);
-            const uint32_t rootS = (tf & 2u) ? ((tf >> 3) & 1u) << 15 : 0x10000u;
-            trow[q] = make_uint4(rr.x, rr.y, (uint32_t)b8[q], rootS | ((tf & 1u) << 14) | ((cnt ? cnt - 1u : 0u) << 17));
-            // W = 1 move row: row word, reset board, and the puzzle the autoreset after it loads
-            if (W == 1) mrow[q] = make_uint4(row1[q].x, (uint32_t)init[q], (uint32_t)(init[q] >> 32),
-                                             q + 1 == P ? 0u : (uint32_t)q + 1u);
-        }
-        HIPCHK(c, hipMalloc(&c->t_trie8, sizeof(uint2) * nn8));
-        HIPCHK(c, hipMemcpy(c->t_trie8, t8.data(), sizeof(uint2) * nn8, hipMemcpyHostToDevice));
-        // look-ahead records (TrieLane::step1la): entry 4k + d = the record of node k's field-d
-        // node (child, or the parent in the back direction), all ones where the field is empty;
-        // at least 4 entries, so that a rootless puzzle's lane (base 0, node 0) reads in bounds
-        std::vector<uint2> tg(4 * nn8, make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu));
-        for (size_t q = 0; q < P; ++q) {
-            const uint32_t* inf = t->info + 4 * q;
-            if (!((inf[1] >> 16) & 2u)) continue;
-            const size_t base = b8[q];
-            const uint32_t cnt = inf[3] & 0xFFFFu;
-            for (uint32_t k = 0; k < cnt; ++k) {
-                const uint2 r = t8[base + k];
-                const uint32_t f[4] = {r.x & 0xFFFFu, r.x >> 16, r.y & 0xFFFFu, r.y >> 16};
-                for (int d = 0; d < 4; ++d)
-                    if (f[d] != 0xFFFFu) tg[4 * (base + k) + d] = t8[base + (f[d] & 0x7FFFu)];
-            }
-        }
-        HIPCHK(c, hipMalloc(&c->t_trieg, sizeof(uint2) * tg.size()));
-        HIPCHK(c, hipMemcpy(c->t_trieg, tg.data(), sizeof(uint2) * tg.size(), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc(&c->t_trow, sizeof(uint4) * P));
-        HIPCHK(c, hipMemcpy(c->t_trow, trow.data(), sizeof(uint4) * P, hipMemcpyHostToDevice));
-        // mixed tables (TrieLaneT<true>): a trie of at most 127 nodes as 4-B records (each 16-bit
-        // field of trie8 as an 8-bit one, index | terminal << 7, 0xFF none), a larger one as its
-        // 8-B records; each puzzle's records start on a 128-B line, the base is a byte offset, and
-        // bit 13 of the row's w marks a compact puzzle (root S then 0x80 / 0x100).  Used when the
-        // 8-B records outgrow an XCD's 4 MB L2: below that the per-lane format costs the trie chain
-        // more than the misses it saves (MI355X, c3: 4,096 puzzles, 2 MB of records, +5 %; 16,384
-        // puzzles, 8.4 MB, -7.4 %; profiles/r06/ab_bigpool); SPARC_VARIANT_MIXED_TRIE overrides
-        c->mixed_pays = nn8 * sizeof(uint2) > kMixedTrieBytes;
-        if (W == 1 && c->mixed_pays) {   // sparc_reset_host refines the choice per XCD (xcd_hot_bytes)
-            c->nodes8.resize(P);
-            for (size_t q = 0; q < P; ++q) c->nodes8[q] = t->info[4 * q + 3] & 0xFFFFu;
-        }
-        if (W == 1) {
-            std::vector<size_t> bo(P, 0);
-            size_t nb = 0;
-            auto tiny = [&](size_t q) { return (t->info[4 * q + 3] & 0xFFFFu) <= 127u; };
-            for (size_t q = 0; q < P; ++q) {
-                if (!((t->info[4 * q + 1] >> 16) & 2u)) continue;
-                nb = (nb + 127u) & ~(size_t)127u;
-                bo[q] = nb;
-                nb += (size_t)(t->info[4 * q + 3] & 0xFFFFu) * (tiny(q) ? 4u : 8u);
-            }
-            nb += 8;   // an 8-B gather of the last 4-B record stays in bounds
-            auto f8 = [](uint32_t f16) { return f16 == 0xFFFFu ? 0xFFu : (f16 & 0x7Fu) | ((f16 >> 15) << 7); };
-            auto rec4 = [&](uint2 r) {
-                return f8(r.x & 0xFFFFu) | (f8(r.x >> 16) << 8) | (f8(r.y & 0xFFFFu) << 16) | (f8(r.y >> 16) << 24);
-            };
-            std::vector<uint8_t> tb(nb, 0xFF);
-            std::vector<uint4> trow4(P);
-            for (size_t q = 0; q < P; ++q) {
-                const uint32_t cnt = t->info[4 * q + 3] & 0xFFFFu;
-                const bool rooted = (t->info[4 * q + 1] >> 16) & 2u, small4 = rooted && tiny(q);
-                const uint32_t w = trow[q].w;
-                uint2 root = make_uint2(trow[q].x, trow[q].y);
-                if (rooted) {
-                    for (uint32_t k = 0; k < cnt; ++k) {
-                        const uint2 r8 = t8[b8[q] + k];
-                        if (small4) {
-                            const uint32_t v = rec4(r8);
-                            memcpy(&tb[bo[q] + 4 * (size_t)k], &v, 4);
-                        } else {
-                            memcpy(&tb[bo[q] + 8 * (size_t)k], &r8, 8);
-                        }
-                    }
-                    if (small4) root = make_uint2(rec4(root), 0xFFFFFFFFu);
-                }
-                // root S 0x80 (terminal) / 0x100 (off the trie) in the compact layout
-                const uint32_t rs = small4 ? ((w & 0x10000u) ? 0x100u : ((w >> 15) & 1u) << 7) : (w & 0x18000u);
-                trow4[q] = make_uint4(root.x, root.y, (uint32_t)bo[q],
-                                      rs | (small4 ? 1u << 13 : 0u) | (w & 0x4000u) | (w & ~0x1FFFFu));
-            }
-            HIPCHK(c, hipMalloc(&c->t_trie4, nb));
-            HIPCHK(c, hipMemcpy(c->t_trie4, tb.data(), nb, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMalloc(&c->t_trow4, sizeof(uint4) * P));
-            HIPCHK(c, hipMemcpy(c->t_trow4, trow4.data(), sizeof(uint4) * P, hipMemcpyHostToDevice));
-        }
-        HIPCHK(c, hipMalloc(&c->t_mrow, sizeof(uint4) * P));
-        HIPCHK(c, hipMemcpy(c->t_mrow, mrow.data(), sizeof(uint4) * P, hipMemcpyHostToDevice));
-        // multi-word split geometry (sparc_movew.hpp): internal pitch + 1, the board plus a
-        // zero row above and one spare dword, the longest possible path in the move stack
-        if (W > 1 && pitch <= 15u) {
-            SplitGeom g{};
-            g.P2 = pitch + 1u;
-            uint32_t xmax = 1, pts = 1;
-            for (size_t q = 0; q < P; ++q) {
-                const uint32_t X = t->info[4 * q] & 0xFFu, Y = (t->info[4 * q] >> 8) & 0xFFu;
-                xmax = std::max(xmax, X);
-                pts = std::max(pts, X * Y);
-            }
-            g.B = ((xmax + 2u) * g.P2 + 31u) / 32u + 1u;
-            g.BS = (g.B + 3u) & ~3u;
-            // the move wave writes slot len - 1 on every step, moved or not, and len reaches pts
-            // on a path through every point: pts slots, not pts - 1
-            g.M = c->cfg.traceback ? ((pts + 15u) & ~15u) : 0u;
-            g.nbr_pos = (2u * g.P2) | ((g.P2 - 1u) << 8) | (0u << 16) | ((g.P2 + 1u) << 24);
-            g.off_board = (uint32_t)kW_Board;
-            g.off_stack = g.off_board + g.BS * 256u;
-            g.pair = (g.off_stack + g.M * 64u + 15u) & ~15u;
-            // the move wave keeps the next reset board in kBoardRegs 16-B registers
-            if (4 * (size_t)g.pair + splitw_fin_bytes() <= kMaxDynLds && g.BS <= 4u * kBoardRegs) {
-                std::vector<uint4> mw(P);
-                std::vector<uint32_t> bw(P * g.BS, 0u);
-                for (size_t q = 0; q < P; ++q) {
-                    const uint32_t* inf = t->info + 4 * q;
-                    const uint32_t X = inf[0] & 0xFF, Y = (inf[0] >> 8) & 0xFF;
-                    const uint32_t sx = (inf[0] >> 16) & 0xFF, sy = inf[0] >> 24;
-                    const uint32_t tx = inf[1] & 0xFF, ty = (inf[1] >> 8) & 0xFF;
-                    mw[q] = make_uint4((sx * g.P2 + sy) | ((tx * g.P2 + ty) << 16), (inf[1] >> 16) & 7u, 0u, 0u);
-                    for (uint32_t x = 0; x < X; ++x)
-                        for (uint32_t y = 0; y < Y; ++y) {
-                            const uint32_t b = x * pitch + y;
-                            if (!((t->open[q * W + (b >> 6)] >> (b & 63)) & 1ull) || (x == sx && y == sy)) continue;
-                            const uint32_t d = (x + 1u) * g.P2 + y;
-                            bw[q * g.BS + (d >> 5)] |= 1u << (d & 31u);
-                        }
-                }
-                HIPCHK(c, hipMalloc(&c->t_mroww, sizeof(uint4) * P));
-                HIPCHK(c, hipMemcpy(c->t_mroww, mw.data(), sizeof(uint4) * P, hipMemcpyHostToDevice));
-                HIPCHK(c, hipMalloc(&c->t_boardw, sizeof(uint32_t) * bw.size()));
-                HIPCHK(c, hipMemcpy(c->t_boardw, bw.data(), sizeof(uint32_t) * bw.size(), hipMemcpyHostToDevice));
-                c->sgeom = g;
-                c->split_w = true;
-            }
-        }
-    }
-    c->ring_ok = W == 1;
-    for (size_t q = 0; q < P; ++q)
-        if ((t->info[4 * q] & 0xFFu) * pitch > kRingShift) c->ring_ok = false;
-    c->num_puzzles = (uint32_t)t->num_puzzles;
-    c->num_nodes = (uint32_t)t->num_nodes;
-    c->h_info.assign(t->info, t->info + 4 * P);
-    // identity of the table for snapshots (sparc_snapshot_info): FNV-1a over the host arrays
-    {
-        uint64_t h = 0xCBF29CE484222325ull;
-        auto mix = [&h](const void* d, size_t bytes) {
-            const uint8_t* b = static_cast<const uint8_t*>(d);
-            for (size_t k = 0; k < bytes; ++k) h = (h ^ b[k]) * 0x100000001B3ull;
-        };
-        const int32_t head[4] = {t->num_puzzles, t->num_nodes, c->cfg.pitch, c->cfg.words};
-        mix(head, sizeof head);
-        mix(t->open, sizeof(uint64_t) * P * W);
-        mix(t->info, sizeof(uint32_t) * 4 * P);
-        if (t->num_nodes > 0) mix(t->trie, sizeof(uint32_t) * 4 * (size_t)t->num_nodes);
-        c->table_hash = h;
-    }
+    c->pz = std::move(d);
     c->loaded = true;
     c->rules = false;       // the rule table indexes the old puzzles
     c->has_state = false;   // old state may point at puzzles that no longer exist
@@ -2690,29 +2380,6 @@ int sparc_reset_device(void* ctx, const uint32_t* d_q, const uint8_t* d_mask, ui
     return SPARC_OK;
 }
 
-// The 8-B trie records one XCD's L2 must hold for the envs of a full reset: k_rollout1s runs 256
-// envs per workgroup and workgroups b, b + 8, ... share an XCD (round-robin dispatch,
-// MI355X_MICROARCH.md), so XCD group g holds envs i with (i / 256) % 8 == g, and each env plays
-// its start puzzle and the next kHotWalk - 1.  Returns the largest group's bytes.  A pool whose
-// envs are placed XCD-locally (bench.initial_puzzles 'xcd') keeps the 8-B records past 4 MB of
-// them (MI355X, c3 at 16,384 puzzles: 0.362 ms with 8-B records against 0.379 ms mixed; the
-// hash placement 0.405 ms, mixed 0.394; profiles/r06/ab_xcd_place).
-static size_t xcd_hot_bytes(const Ctx* c, const uint32_t* q) {
-    const uint32_t P = c->num_puzzles;
-    std::vector<uint8_t> seen(P, 0);   // bit g: counted for group g
-    size_t bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (uint32_t i = 0; i < c->n; ++i) {
-        const uint32_t g = (i / 256u) & 7u;
-        uint32_t u = q[i];
-        for (uint32_t k = 0; k < kHotWalk; ++k, u = u + 1 == P ? 0u : u + 1) {
-            if (seen[u] & (1u << g)) continue;
-            seen[u] |= (uint8_t)(1u << g);
-            bytes[g] += (size_t)c->nodes8[u] * sizeof(uint2);
-        }
-    }
-    return *std::max_element(bytes, bytes + 8);
-}
-
 int sparc_reset_host(void* ctx, const uint32_t* q, const uint8_t* mask, uint8_t* flags) {
     DevGuard dg;
     Ctx* c = static_cast<Ctx*>(ctx);
@@ -2720,13 +2387,14 @@ int sparc_reset_host(void* ctx, const uint32_t* q, const uint8_t* mask, uint8_t*
     if (rc) return rc;
     if (!q) return fail(c, SPARC_E_INVALID, "null puzzle_index");
     for (uint32_t i = 0; i < c->n; ++i)
-        if ((!mask || mask[i]) && q[i] >= c->num_puzzles) return fail(c, SPARC_E_INVALID, "puzzle index out of range");
-    if (!mask && c->nodes8.size() == c->num_puzzles) c->mixed_pays = xcd_hot_bytes(c, q) > kMixedTrieBytes;
-    HIPCHK(c, hipMemcpyAsync(c->s_pidx, q, sizeof(uint32_t) * c->n, hipMemcpyHostToDevice, c->stream));
-    if (mask) HIPCHK(c, hipMemcpyAsync(c->s_mask, mask, c->n, hipMemcpyHostToDevice, c->stream));
-    rc = sparc_reset_device(c, c->s_pidx, mask ? c->s_mask : nullptr, flags ? c->s_flags : nullptr);
+        if ((!mask || mask[i]) && q[i] >= c->pz.num_puzzles) return fail(c, SPARC_E_INVALID, "puzzle index out of range");
+    if (!mask && c->pz.nodes8.size() == c->pz.num_puzzles)
+        c->pz.mixed_pays = xcd_hot_bytes(c->pz.nodes8, q, c->n) > kMixedTrieBytes;
+    HIPCHK(c, hipMemcpyAsync(c->s_pidx.get(), q, sizeof(uint32_t) * c->n, hipMemcpyHostToDevice, c->stream));
+    if (mask) HIPCHK(c, hipMemcpyAsync(c->s_mask.get(), mask, c->n, hipMemcpyHostToDevice, c->stream));
+    rc = sparc_reset_device(c, c->s_pidx.get(), mask ? c->s_mask.get() : nullptr, flags ? c->s_flags.get() : nullptr);
     if (rc) return rc;
-    if (flags) HIPCHK(c, hipMemcpyAsync(flags, c->s_flags, c->n, hipMemcpyDeviceToHost, c->stream));
+    if (flags) HIPCHK(c, hipMemcpyAsync(flags, c->s_flags.get(), c->n, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 
@@ -2750,11 +2418,11 @@ int sparc_step_host(void* ctx, const uint8_t* act, int8_t* rew, uint8_t* flags) 
     int rc = check_ctx(c, true);
     if (rc) return rc;
     if (!act || !rew || !flags) return fail(c, SPARC_E_INVALID, "null argument");
-    HIPCHK(c, hipMemcpyAsync(c->s_act, act, c->n, hipMemcpyHostToDevice, c->stream));
-    rc = sparc_step_device(c, c->s_act, c->s_rew, c->s_flags);
+    HIPCHK(c, hipMemcpyAsync(c->s_act.get(), act, c->n, hipMemcpyHostToDevice, c->stream));
+    rc = sparc_step_device(c, c->s_act.get(), c->s_rew.get(), c->s_flags.get());
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(rew, c->s_rew, c->n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(flags, c->s_flags, c->n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rew, c->s_rew.get(), c->n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(flags, c->s_flags.get(), c->n, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 
@@ -2778,7 +2446,7 @@ int sparc_random_actions_device(void* ctx, int32_t T, uint64_t seed, uint64_t t0
 namespace {
 // rule rollouts that run k_rollout1r (W = 1 pools whose every puzzle has a region-code table and
 // whose boards fit the ring word); the rest run the generic k_rollout<..., RULES>
-bool r1r_rollout(const Ctx* c) { return c->W == 1 && c->r_tab_all && c->ring_ok && !c->rules_generic; }
+bool r1r_rollout(const Ctx* c) { return c->W == 1 && c->rl.tab_all && c->pz.ring_ok && !c->rules_generic; }
 
 // sparc_rollout_device / sparc_rollout_obs_device; `ot` non-null: observation traces
 int rollout_impl(Ctx* c, int32_t T, const uint8_t* d_act, uint64_t seed, uint64_t t0, int8_t* d_rew,
@@ -2805,23 +2473,23 @@ int rollout_impl(Ctx* c, int32_t T, const uint8_t* d_act, uint64_t seed, uint64_
         const size_t blocks = (c->n + 255) / 256;
         const size_t per_cu = (blocks + 255) / 256;
         const size_t budget = std::min(kMaxDynLds, (size_t)160 * 1024 / (per_cu ? per_cu : 1));
-        const size_t tbytes = table_lds_bytes<1>(c->num_puzzles);
+        const size_t tbytes = table_lds_bytes<1>(c->pz.num_puzzles);
         // the full tiles of full workgroups go through the split move / trie kernel (MI355X, c3
         // at 65,536 envs: 0.266 vs 0.312 ms per 1,000 steps); a tail of T % 16 steps or a batch
         // that is not a multiple of 256 envs goes through k_rollout1 below
-        if (tiled && c->n % 256 == 0 && T >= kTile && c->t_trie8 && split1_pitch_ok((uint32_t)c->cfg.pitch)) {
+        if (tiled && c->n % 256 == 0 && T >= kTile && c->pz.trie8 && split1_pitch_ok((uint32_t)c->cfg.pitch)) {
             const int32_t T16 = T / kTile * kTile;
-            const size_t sbytes = split_table_bytes(c->num_puzzles);
+            const size_t sbytes = split_table_bytes(c->pz.num_puzzles);
             const bool lds_s = kS_Base + sbytes <= budget;
             // past the row budget: rows from the L2, the trie rows handed over through slots
             const size_t shm_s = kS_Base + (lds_s ? sbytes : kS_SlotBytes);
             // past the row budget the mixed tables (tries of at most 127 nodes in 4-B records:
             // twice the nodes per L2 line; sparc_trie.hpp TrieLaneT<true>)
-            const bool compact = !lds_s && c->t_trie4 && (c->mixed_trie == 1 || (c->mixed_trie == 0 && c->mixed_pays));
+            const bool compact = !lds_s && c->pz.trie4 && (c->mixed_trie == 1 || (c->mixed_trie == 0 && c->pz.mixed_pays));
             Params ps = p;
             if (compact) {
-                ps.tab.trie8 = reinterpret_cast<const uint2*>(c->t_trie4);
-                ps.tab.trow = c->t_trow4;
+                ps.tab.trie8 = reinterpret_cast<const uint2*>(c->pz.trie4.get());
+                ps.tab.trow = c->pz.trow4.get();
             }
             auto launch_s = [&](auto kern, const uint8_t* a) {
                 if (shm_s > 64 * 1024 && (lds_rc = allow_big_lds(c, reinterpret_cast<const void*>(kern)))) return;
@@ -2900,7 +2568,7 @@ int rollout_impl(Ctx* c, int32_t T, const uint8_t* d_act, uint64_t seed, uint64_
             constexpr bool INC = Geo::INC;
             using GG = R1Geom<G, A, RT>;
             const size_t blocks = (c->n + GG::kEnvs - 1) / GG::kEnvs;
-            const size_t tbytes = table_lds_bytes<1>(c->num_puzzles);
+            const size_t tbytes = table_lds_bytes<1>(c->pz.num_puzzles);
             // the puzzle rows go to LDS only while a 12-wave workgroup still leaves room for a
             // second one on the CU (80 KB each); past that the step waves read them from the L2
             // (their resets have slack: the audit waves set the pace)
@@ -2945,22 +2613,22 @@ int rollout_impl(Ctx* c, int32_t T, const uint8_t* d_act, uint64_t seed, uint64_
         if (lds_rc) return lds_rc;
         return launch_check(c);
     }
-    if (c->W > 1 && !ot && !rtr && c->split_w && tiled && c->n % 256 == 0 && T >= kTile) {
+    if (c->W > 1 && !ot && !rtr && c->pz.split_w && tiled && c->n % 256 == 0 && T >= kTile) {
         // the full tiles of whole 256-env workgroups go through the multi-word split kernel; a
         // tail of T % 16 steps through k_rollout below (the state round-trips HBM exactly)
         const int32_t T16 = T / kTile * kTile;
-        const SplitGeom& g = c->sgeom;
+        const SplitGeom& g = c->pz.sgeom;
         const size_t blocks = c->n / 256;
         const size_t base = 4 * (size_t)g.pair + splitw_fin_bytes();
-        const bool lds_t = base + sizeof(uint4) * c->num_puzzles <= kMaxDynLds;
-        const size_t shm = base + (lds_t ? sizeof(uint4) * c->num_puzzles : 0);
+        const bool lds_t = base + sizeof(uint4) * c->pz.num_puzzles <= kMaxDynLds;
+        const size_t shm = base + (lds_t ? sizeof(uint4) * c->pz.num_puzzles : 0);
         dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
             constexpr int W = decltype(w)::value;
             constexpr bool TB = decltype(tb)::value;
             if constexpr (W > 1) {
                 auto launch = [&](auto kern, const uint8_t* a) {
                     if (shm > 64 * 1024 && (lds_rc = allow_big_lds(c, reinterpret_cast<const void*>(kern)))) return;
-                    kern<<<dim3((unsigned)blocks), kBlock1s, shm, c->stream>>>(p, g, c->t_mroww, c->t_boardw, T16, a, seed,
+                    kern<<<dim3((unsigned)blocks), kBlock1s, shm, c->stream>>>(p, g, c->pz.mroww.get(), c->pz.boardw.get(), T16, a, seed,
                                                                               t0, d_rew, d_flags, st);
                 };
                 auto go = [&](auto ior) {
@@ -3019,7 +2687,7 @@ int rollout_impl(Ctx* c, int32_t T, const uint8_t* d_act, uint64_t seed, uint64_
             const size_t budget = std::min(kMaxDynLds, (size_t)160 * 1024 / (per_cu ? per_cu : 1));
             const size_t base = tiles_lds_bytes<W, EPW>() + stack_lds_bytes<W, TB, EPW>() + (OBS ? obs_lds_bytes<W>() : 0) +
                                 (RULES ? bits_lds_bytes<EPW>() : 0);
-            const size_t tbytes = table_lds_bytes<W>(c->num_puzzles);
+            const size_t tbytes = table_lds_bytes<W>(c->pz.num_puzzles);
             const bool lds_table = base + tbytes <= budget;
             const size_t shm = base + (lds_table ? tbytes : 0);
             const dim3 g((unsigned)blocks);
@@ -3051,21 +2719,16 @@ int rollout_impl(Ctx* c, int32_t T, const uint8_t* d_act, uint64_t seed, uint64_
 int snapshot(Ctx* c, int32_t* d_stats, bool save) {
     const size_t n = c->n, W = (size_t)c->W;
     const std::pair<void*, size_t> parts[] = {
-        {c->vis, 8 * W * n}, {c->dirs, c->cfg.traceback ? 16 * W * n : 0}, {c->pos, 4 * n}, {c->aux, 4 * n},
-        {c->step, 4 * n}, {c->pid, 4 * n}, {c->r_memo, sizeof(FitMemo<kMemo>) * n}, {d_stats, d_stats ? 16 * n : 0}};
+        {c->vis.get(), 8 * W * n}, {c->dirs.get(), c->cfg.traceback ? 16 * W * n : 0}, {c->pos.get(), 4 * n},
+        {c->aux.get(), 4 * n}, {c->step.get(), 4 * n}, {c->pid.get(), 4 * n},
+        {c->r_memo.get(), sizeof(FitMemo<kMemo>) * n}, {d_stats, d_stats ? 16 * n : 0}};
     size_t total = 0;
     for (const auto& pt : parts) total += (pt.first ? pt.second : 0);
-    if (save && total > c->snap_bytes) {
-        if (c->snap) HIPCHK(c, hipFree(c->snap));
-        c->snap = nullptr;
-        c->snap_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->snap, total));
-        c->snap_bytes = total;
-    }
+    if (save) HIPCHK(c, c->snap.reserve(total));
     size_t off = 0;
     for (const auto& pt : parts) {
         if (!pt.first || !pt.second) continue;
-        uint8_t* sp = static_cast<uint8_t*>(c->snap) + off;
+        uint8_t* sp = c->snap.get() + off;
         if (save) HIPCHK(c, hipMemcpyAsync(sp, pt.first, pt.second, hipMemcpyDeviceToDevice, c->stream));
         else HIPCHK(c, hipMemcpyAsync(pt.first, sp, pt.second, hipMemcpyDeviceToDevice, c->stream));
         off += pt.second;
@@ -3076,7 +2739,7 @@ int snapshot(Ctx* c, int32_t* d_stats, bool save) {
 // launch the recorded audit call (sparc_rules_device / sparc_rollout_rules_device)
 int launch_rules(Ctx* c, const AuditCall& a) {
     if (a.kind == 2) {
-        const RuleTrace rtr{rules_tab(c, true), a.bits, c->r_memo};
+        const RuleTrace rtr{rules_tab(c, c->rl, true), a.bits, c->r_memo.get()};
         const bool generic = c->rules_generic;
         if (a.snap) c->rules_generic = true;   // the kernel the call was recorded with
         const int rc = rollout_impl(c, a.T, a.act, a.seed, a.t0, a.rew, a.flags, a.stats, nullptr, &rtr);
@@ -3084,11 +2747,11 @@ int launch_rules(Ctx* c, const AuditCall& a) {
         return rc;
     }
     const Params p = make_params(c);
-    const RulesTab rt = rules_tab(c, true);
+    const RulesTab rt = rules_tab(c, c->rl, true);
     const dim3 g = grid_for(c->n);
-    if (c->W == 1) k_rules<1><<<g, kBlock, 0, c->stream>>>(p, rt, a.bits, a.region, a.fit, c->r_memo);
-    else if (c->W == 2) k_rules<2><<<g, kBlock, 0, c->stream>>>(p, rt, a.bits, a.region, a.fit, c->r_memo);
-    else k_rules<4><<<g, kBlock, 0, c->stream>>>(p, rt, a.bits, a.region, a.fit, c->r_memo);
+    if (c->W == 1) k_rules<1><<<g, kBlock, 0, c->stream>>>(p, rt, a.bits, a.region, a.fit, c->r_memo.get());
+    else if (c->W == 2) k_rules<2><<<g, kBlock, 0, c->stream>>>(p, rt, a.bits, a.region, a.fit, c->r_memo.get());
+    else k_rules<4><<<g, kBlock, 0, c->stream>>>(p, rt, a.bits, a.region, a.fit, c->r_memo.get());
     return launch_check(c);
 }
 
@@ -3128,7 +2791,7 @@ int sparc_rollout_rules_device(void* ctx, int32_t T, const uint8_t* d_act, uint6
     if (!c->rules) return fail(c, SPARC_E_STATE, "sparc_load_rules has not been called");
     if (!d_rule_bits) return fail(c, SPARC_E_INVALID, "null rule_bits");
     if (T < 0) return fail(c, SPARC_E_INVALID, "T must be >= 0");
-    HIPCHK(c, hipMemsetAsync(c->fq_count, 0, sizeof(*c->fq_count), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->fq_count.get(), 0, sizeof(unsigned long long), c->stream));
     AuditCall a;
     a.kind = 2;
     a.extent = (uint64_t)T * c->n;
@@ -3212,206 +2875,82 @@ int sparc_obs_pack_device(void* ctx, int32_t* d_vis, int32_t* d_agent, int32_t x
     return launch_check(c);
 }
 
+// As sparc_load_puzzles: build on the host, upload into a local RuleDev (the region-code table is
+// computed on it too), commit last.  A failing call leaves the loaded rule table in place.
 int sparc_load_rules(void* ctx, const sparc_rules_table* t) {
     DevGuard dg;
     Ctx* c = static_cast<Ctx*>(ctx);
     int rc = check_ctx(c, false);
     if (rc) return rc;
-    if (!t || !t->planes || !t->inst_first || !t->shape_first) return fail(c, SPARC_E_INVALID, "null argument");
-    if ((uint32_t)t->num_puzzles != c->num_puzzles)
-        return fail(c, SPARC_E_INVALID, "rule table puzzle count differs from the loaded puzzle table");
-    if (t->num_inst < 0 || t->num_shapes < 0 || t->num_offsets < 0 || t->num_shapes >= (1 << 21) ||
-        (t->num_inst && !t->inst) || (t->num_shapes && !t->shape_area) || (t->num_offsets && !t->shape_off))
-        return fail(c, SPARC_E_INVALID, "bad rule table sizes");
     const int W = c->W;
-    const size_t P = (size_t)t->num_puzzles, S = (size_t)t->num_shapes;
-    std::vector<uint4> info(P);
-    HIPCHK(c, hipMemcpy(info.data(), c->t_info, sizeof(uint4) * P, hipMemcpyDeviceToHost));
-    // the device's ranges: {first, count} per shape and {first, count | kHostFit} per puzzle
-    std::vector<uint2> srange(std::max<size_t>(1, S), make_uint2(0u, 0u)), ifc(P);
-    if (t->shape_first[0] != 0) return fail(c, SPARC_E_INVALID, "shape offsets must start at 0");
-    for (size_t sh = 0; sh < S; ++sh) {
-        const uint32_t o0 = t->shape_first[sh], o1 = t->shape_first[sh + 1];
-        if (o1 < o0 || o1 > (uint32_t)t->num_offsets) return fail(c, SPARC_E_INVALID, "shape offsets out of range");
-        srange[sh] = make_uint2(o0, o1 - o0);
-    }
-    if (t->inst_first[0] != 0) return fail(c, SPARC_E_INVALID, "instance offsets must start at 0");
-    size_t host_fit_puzzles = 0;
-    for (size_t q = 0; q < P; ++q) {
-        const uint32_t X = info[q].x & 0xFFu, Y = (info[q].x >> 8) & 0xFFu;
-        const uint32_t f = t->inst_first[q], f1 = t->inst_first[q + 1];
-        char m[160];
-        if (X > 15 || Y > 15) {
-            snprintf(m, sizeof m, "puzzle %zu: the rule audit supports lattices up to 15x15", q);
-            return fail(c, SPARC_E_INVALID, m);
-        }
-        if (f1 < f || f1 > (uint32_t)t->num_inst) return fail(c, SPARC_E_INVALID, "instance range out of bounds");
-        const uint32_t n = f1 - f;
-        const uint32_t cells = ((X - 1) / 2) * ((Y - 1) / 2);
-        if (n > cells) {   // _extract_poly_instances: one instance per cell centre
-            snprintf(m, sizeof m, "puzzle %zu: %u instances on %u cells", q, n, cells);
-            return fail(c, SPARC_E_INVALID, m);
-        }
-        int ny = 0, nd = 0;
-        uint32_t ds[kHostFitMax];
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t e = t->inst[f + k], b = e & 0x3FFu, sh = e >> 11;
-            if (b >= 64u * W || sh >= (uint32_t)S) return fail(c, SPARC_E_INVALID, "bad instance");
-            if ((e >> 10) & 1u) { ++ny; continue; }
-            int j = 0;
-            while (j < nd && ds[j] != sh) ++j;
-            if (j == nd) ds[nd++] = sh;
-        }
-        // past the GPU search's list sizes: the puzzle's searches run on the host (kHostFit)
-        const bool hf = ny > kFitYlops || nd > kFitShapes;
-        host_fit_puzzles += hf;
-        ifc[q] = make_uint2(f, n | (hf ? kHostFit : 0u));
-    }
-    void* old[] = {c->r_planes, c->r_inst_fc, c->r_inst, c->r_shape_range, c->r_shape_area, c->r_shape_off,
-                   c->r_reg_off, c->r_reg_tab, c->r_rows};
-    for (void* b : old)
-        if (b) HIPCHK(c, hipFree(b));
-    c->r_planes = nullptr; c->r_inst_fc = nullptr; c->r_inst = nullptr;
-    c->r_shape_range = nullptr; c->r_shape_area = nullptr; c->r_shape_off = nullptr;
-    c->r_reg_off = nullptr; c->r_reg_tab = nullptr; c->r_rows = nullptr;
-    c->rules = false;
-    c->r_tab_all = false;
-    c->host_fit_puzzles = host_fit_puzzles;
-    // the device copy: the caller's SPARC_RULE_PLANES planes per puzzle, RP_INST rewritten from the
-    // instance list, then the bit-sliced net area of each cell (kAreaPlanes planes, sparc_rules.hpp)
-    static_assert(RP_ABI == SPARC_RULE_PLANES, "rule plane layout");
-    const size_t np_ = P * RP_COUNT * W;
-    std::vector<uint64_t> dev_planes(np_, 0ull);
-    bool area_ok = true;
-    for (size_t q = 0; q < P; ++q) {
-        uint64_t* d = dev_planes.data() + q * RP_COUNT * W;
-        std::copy(t->planes + q * RP_ABI * W, t->planes + (q + 1) * RP_ABI * W, d);
-        for (int k = 0; k < W; ++k) d[RP_INST * W + k] = 0;
-        int32_t net[256] = {0};
-        const uint32_t f = ifc[q].x, n = ifc[q].y & ~kHostFit;
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t e = t->inst[f + k], b = e & 0x3FFu;
-            const int64_t a = t->shape_area[e >> 11];
-            net[b] = (int32_t)std::max<int64_t>(-(1 << 20), std::min<int64_t>(1 << 20, net[b] + (((e >> 10) & 1u) ? -a : a)));
-            d[RP_INST * W + (b >> 6)] |= 1ull << (b & 63);
-        }
-        for (uint32_t b = 0; b < 64u * W; ++b) {
-            if (net[b] < -(1 << (kAreaPlanes - 1)) || net[b] >= (1 << (kAreaPlanes - 1))) area_ok = false;
-            for (int k = 0; k < kAreaPlanes; ++k)
-                if (((uint32_t)net[b] >> k) & 1u) d[(RP_AREA0 + k) * W + (b >> 6)] |= 1ull << (b & 63);
-        }
-    }
-    const size_t ni = std::max<size_t>(1, t->num_inst), ns = std::max<size_t>(1, t->num_shapes),
-                 no = std::max<size_t>(1, t->num_offsets);
-    HIPCHK(c, hipMalloc(&c->r_planes, sizeof(uint64_t) * np_));
-    HIPCHK(c, hipMalloc(&c->r_inst_fc, sizeof(uint2) * P));
-    HIPCHK(c, hipMalloc(&c->r_inst, sizeof(uint32_t) * ni));
-    HIPCHK(c, hipMalloc(&c->r_shape_range, sizeof(uint2) * ns));
-    HIPCHK(c, hipMalloc(&c->r_shape_area, sizeof(int32_t) * ns));
-    HIPCHK(c, hipMalloc(&c->r_shape_off, 2 * no));
-    HIPCHK(c, hipMemcpy(c->r_planes, dev_planes.data(), sizeof(uint64_t) * np_, hipMemcpyHostToDevice));
-    c->r_area = area_ok;   // a cell's net area outside -128..127: the audit walks the list instead
-    HIPCHK(c, hipMemcpy(c->r_inst_fc, ifc.data(), sizeof(uint2) * P, hipMemcpyHostToDevice));
-    if (t->num_inst) HIPCHK(c, hipMemcpy(c->r_inst, t->inst, sizeof(uint32_t) * t->num_inst, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->r_shape_range, srange.data(), sizeof(uint2) * ns, hipMemcpyHostToDevice));
-    if (S) HIPCHK(c, hipMemcpy(c->r_shape_area, t->shape_area, sizeof(int32_t) * S, hipMemcpyHostToDevice));
-    if (t->num_offsets) HIPCHK(c, hipMemcpy(c->r_shape_off, t->shape_off, 2 * (size_t)t->num_offsets, hipMemcpyHostToDevice));
-    // host copies for the exact fits the host finishes (searches past the node cap, kHostFit puzzles)
-    c->h_inst.assign(t->inst, t->inst + t->num_inst);
-    c->h_inst.resize(ni, 0u);
-    c->h_inst_fc = ifc;
-    c->h_shape_range = srange;
-    c->h_shape_off.assign(t->shape_off, t->shape_off + 2 * (size_t)t->num_offsets);
-    c->h_shape_off.resize(2 * no, 0);
-    if (!c->fq_count) {
-        HIPCHK(c, hipMalloc(&c->fq_count, sizeof(*c->fq_count)));
-        HIPCHK(c, hipMalloc(&c->fq_items, sizeof(FitTodo) * kFitQueueCap));
-        c->fq_cap = kFitQueueCap;
-    }
-    HIPCHK(c, hipMemset(c->fq_count, 0, sizeof(*c->fq_count)));
-    c->last_audit = AuditCall{};
-    // the host's answers name puzzles of the old table
-    c->hf_used = 0;
-    std::fill(c->h_hf.begin(), c->h_hf.end(), make_uint4(0u, 0u, 0u, 0u));
-    // the memo's entries name puzzles of the old table: start empty (a zero key matches no region)
-    if (!c->r_memo) HIPCHK(c, hipMalloc(&c->r_memo, sizeof(FitMemo<kMemo>) * (size_t)c->n));
-    HIPCHK(c, hipMemset(c->r_memo, 0, sizeof(FitMemo<kMemo>) * (size_t)c->n));
-    // the per-region check code (squares, stars, poly/ylop area + exact fit) of every region cell
-    // mask of each puzzle with at most kRegTabCells cells, computed once here by the audit's own
-    // region_code (k_region_table): the audit then looks codes up per region instead of running
-    // the checks (the memo serves the larger puzzles, and the puzzles past the table budget:
-    // 2^28 entries, 128 MB, unless sparc_set_rule_limits sets another).  An exact fit that passes
-    // the node cap here is finished on the host, so the table holds only final answers.
-    std::vector<uint32_t> reg_off(P, kNoRegTab);
-    std::vector<uint2> items;
-    size_t entries = 0;
-    const size_t kMaxRegEntries = c->reg_entries;
-    for (size_t q = 0; q < P; ++q) {
-        const uint32_t X = info[q].x & 0xFFu, Y = (info[q].x >> 8) & 0xFFu;
-        const uint32_t cells = ((X - 1) / 2) * ((Y - 1) / 2);
-        if (cells > kRegTabCells) continue;
-        const uint32_t words = cells <= 3 ? 1u : 1u << (cells - 3);
-        if (entries + 8u * words > kMaxRegEntries) break;
-        reg_off[q] = (uint32_t)entries;
-        for (uint32_t g = 0; g < words; ++g) items.push_back(make_uint2((uint32_t)q, g));
-        entries += 8u * words;
-    }
-    c->r_tab_all = std::none_of(reg_off.begin(), reg_off.end(), [](uint32_t o) { return o == kNoRegTab; });
-    if (!items.empty()) {
-        const size_t words = entries / 8;
-        uint2* d_items = nullptr;
-        HIPCHK(c, hipMalloc(&c->r_reg_off, sizeof(uint32_t) * P));
-        HIPCHK(c, hipMalloc(&c->r_reg_tab, sizeof(uint32_t) * words));
-        HIPCHK(c, hipMalloc(&d_items, sizeof(uint2) * items.size()));
-        HIPCHK(c, hipMemcpy(c->r_reg_off, reg_off.data(), sizeof(uint32_t) * P, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(d_items, items.data(), sizeof(uint2) * items.size(), hipMemcpyHostToDevice));
+    HostRuleTables h;
+    if (const BuildError e = build_rule_tables(t, c->pz.h_info, W, c->reg_entries, h)) return fail(c, e.code, e.msg);
+    RuleDev r;
+    HIPCHK(c, upload(r.planes, h.planes));
+    HIPCHK(c, upload(r.inst_fc, h.inst_fc));
+    HIPCHK(c, upload(r.inst, h.inst));
+    HIPCHK(c, upload(r.shape_range, h.shape_range));
+    HIPCHK(c, upload(r.shape_area, h.shape_area));
+    HIPCHK(c, upload(r.shape_off, h.shape_off));
+    r.area = h.area_ok;
+    r.tab_all = h.tab_all;
+    r.host_fit_puzzles = h.host_fit_puzzles;
+    r.h_inst = std::move(h.inst);
+    r.h_inst_fc = h.inst_fc;
+    r.h_shape_range = std::move(h.shape_range);
+    r.h_shape_off = std::move(h.shape_off);
+    // the audits' scratch outlives a rule table: the queue, and the per-env memo
+    if (!c->fq_count.get()) HIPCHK(c, c->fq_count.alloc(1));
+    HIPCHK(c, c->fq_items.reserve(kFitQueueCap));
+    HIPCHK(c, c->r_memo.reserve(c->n));
+    HIPCHK(c, hipMemset(c->fq_count.get(), 0, sizeof(unsigned long long)));
+    // the region-code table, by the audit's own region_code (k_region_table).  An exact fit that
+    // passes the node cap here is finished on the host, so the table holds only final answers.
+    if (!h.items.empty()) {
+        DevBuf<uint2> d_items;
+        HIPCHK(c, upload(r.reg_off, h.reg_off));
+        HIPCHK(c, r.reg_tab.alloc(h.reg_words));
+        HIPCHK(c, upload(d_items, h.items));
         const Params p = make_params(c);
-        RulesTab rt = rules_tab(c, false);
+        RulesTab rt = rules_tab(c, r, false);
         rt.reg_tab = nullptr;
-        const dim3 g((unsigned)((items.size() + kBlock - 1) / kBlock));
-        const uint32_t n_items = (uint32_t)items.size();
-        if (W == 1) k_region_table<1><<<g, kBlock, 0, c->stream>>>(p, rt, d_items, n_items, c->r_reg_tab, c->fq_count);
-        else if (W == 2) k_region_table<2><<<g, kBlock, 0, c->stream>>>(p, rt, d_items, n_items, c->r_reg_tab, c->fq_count);
-        else k_region_table<4><<<g, kBlock, 0, c->stream>>>(p, rt, d_items, n_items, c->r_reg_tab, c->fq_count);
+        rt.hf = HostFits{nullptr, 0u, 0u};   // the host's answers name the old table
+        const dim3 g((unsigned)((h.items.size() + kBlock - 1) / kBlock));
+        const uint32_t n_items = (uint32_t)h.items.size();
+        if (W == 1) k_region_table<1><<<g, kBlock, 0, c->stream>>>(p, rt, d_items.get(), n_items, r.reg_tab.get(), c->fq_count.get());
+        else if (W == 2) k_region_table<2><<<g, kBlock, 0, c->stream>>>(p, rt, d_items.get(), n_items, r.reg_tab.get(), c->fq_count.get());
+        else k_region_table<4><<<g, kBlock, 0, c->stream>>>(p, rt, d_items.get(), n_items, r.reg_tab.get(), c->fq_count.get());
         rc = launch_check(c);
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(d_items));
         if (rc) return rc;
         unsigned long long exhausted = 0;
-        HIPCHK(c, hipMemcpy(&exhausted, c->fq_count, sizeof(exhausted), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&exhausted, c->fq_count.get(), sizeof(exhausted), hipMemcpyDeviceToHost));
         if (exhausted) {   // finish those searches on the host and rewrite their codes
-            HIPCHK(c, hipMemset(c->fq_count, 0, sizeof(*c->fq_count)));
-            std::vector<uint32_t> tab(words);
-            HIPCHK(c, hipMemcpy(tab.data(), c->r_reg_tab, sizeof(uint32_t) * words, hipMemcpyDeviceToHost));
-            parallel_for(items.size(), [&](size_t k) {   // each word belongs to one item
-                const uint2 it = items[k];
-                uint32_t& w = tab[reg_off[it.x] / 8u + it.y];
+            HIPCHK(c, hipMemset(c->fq_count.get(), 0, sizeof(unsigned long long)));
+            std::vector<uint32_t> tab(h.reg_words);
+            HIPCHK(c, hipMemcpy(tab.data(), r.reg_tab.get(), sizeof(uint32_t) * h.reg_words, hipMemcpyDeviceToHost));
+            parallel_for(h.items.size(), [&](size_t k) {   // each word belongs to one item
+                const uint2 it = h.items[k];
+                uint32_t& w = tab[h.reg_off[it.x] / 8u + it.y];
                 for (uint32_t j = 0; j < 8; ++j) {
                     const uint32_t sh = 4u * j + kRcPolyShift;
                     if (((w >> sh) & 3u) != 3u) continue;
-                    const uint32_t poly = host_fit(c, it.x, 8ull * it.y + j) ? 1u : 2u;
+                    const uint32_t poly = host_fit(c, r, it.x, 8ull * it.y + j) ? 1u : 2u;
                     w = (w & ~(3u << sh)) | (poly << sh);
                 }
             });
-            HIPCHK(c, hipMemcpy(c->r_reg_tab, tab.data(), sizeof(uint32_t) * words, hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(r.reg_tab.get(), tab.data(), sizeof(uint32_t) * h.reg_words, hipMemcpyHostToDevice));
         }
     }
-    // the audit's per-puzzle rows (RulesTab::rows): base planes, table offset, instance range, info
-    {
-        const size_t RW = W == 1 ? rule_row_u64<1>() : W == 2 ? rule_row_u64<2>() : rule_row_u64<4>();
-        std::vector<uint64_t> rows(P * RW, 0ull);
-        for (size_t q = 0; q < P; ++q) {
-            uint64_t* r = rows.data() + q * RW;
-            for (int k = 0; k < 10; ++k)
-                for (int w = 0; w < W; ++w) r[k * W + w] = dev_planes[(q * RP_COUNT + kBasePlanes[k]) * W + w];
-            // info.y bits 24-31 (free: flags use 16-18) carry the instance count | kHostFit << 7
-            const uint32_t cf = (ifc[q].y & 0x7Fu) | ((ifc[q].y & kHostFit) ? 0x80u : 0u);
-            r[10 * W] = (uint64_t)reg_off[q] | ((uint64_t)ifc[q].x << 32);
-            r[10 * W + 1] = (uint64_t)info[q].x | ((uint64_t)((info[q].y & 0x00FFFFFFu) | (cf << 24)) << 32);
-        }
-        HIPCHK(c, hipMalloc(&c->r_rows, sizeof(uint64_t) * rows.size()));
-        HIPCHK(c, hipMemcpy(c->r_rows, rows.data(), sizeof(uint64_t) * rows.size(), hipMemcpyHostToDevice));
-    }
+    HIPCHK(c, upload(r.rows, build_rule_rows(h, c->pz.h_info, W)));
+    // the memo's entries and the host's answers name puzzles of the old table: start empty (a zero
+    // memo key matches no region)
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // no launch still reads the old table
+    HIPCHK(c, hipMemset(c->r_memo.get(), 0, sizeof(FitMemo<kMemo>) * (size_t)c->n));
+    c->rl = std::move(r);
+    c->hf_used = 0;
+    std::fill(c->h_hf.begin(), c->h_hf.end(), make_uint4(0u, 0u, 0u, 0u));
+    c->last_audit = AuditCall{};
     c->rules = true;
     return SPARC_OK;
 }
@@ -3421,62 +2960,34 @@ int sparc_load_rules(void* ctx, const sparc_rules_table* t) {
 namespace {
 // per-env audit outputs of the host-pointer / one-env calls (device scratch)
 int audit_scratch(Ctx* c) {
-    if (c->s_bits) return SPARC_OK;
     const size_t n = c->n;
-    HIPCHK(c, hipMalloc(&c->s_bits, 2 * n));
-    HIPCHK(c, hipMalloc(&c->s_region, n * 64 * c->W));
-    HIPCHK(c, hipMalloc(&c->s_fit, 8 * n));
+    HIPCHK(c, c->s_bits.reserve(n));
+    HIPCHK(c, c->s_region.reserve(n * 64 * c->W));
+    HIPCHK(c, c->s_fit.reserve(n));
     return SPARC_OK;
 }
 
 // the FitQueue count of the last audit call (one stream sync)
 int read_queue_count(Ctx* c, uint64_t& n) {
-    if (!c->h_count) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_count), sizeof(uint64_t), hipHostMallocDefault));
-    HIPCHK(c, hipMemcpyAsync(c->h_count, c->fq_count, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, c->h_count.ensure(hipHostMallocDefault));
+    HIPCHK(c, hipMemcpyAsync(c->h_count.get(), c->fq_count.get(), sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    n = *c->h_count;
+    n = *c->h_count.get();
     return SPARC_OK;
 }
 
-// one answer into the host mirror of HostFits (false: already there)
-bool hostfits_insert(std::vector<uint4>& t, uint32_t q, uint64_t rm, uint32_t fits) {
-    const uint32_t mask = (uint32_t)t.size() - 1u;
-    for (uint32_t s = hostfit_slot(q, rm, mask);; s = (s + 1u) & mask) {
-        uint4& e = t[s];
-        if (!(e.w & 2u)) {
-            e = make_uint4((uint32_t)rm, (uint32_t)(rm >> 32), q, fits | 2u);
-            return true;
-        }
-        if (e.x == (uint32_t)rm && e.y == (uint32_t)(rm >> 32) && e.z == q) return false;
-    }
-}
-
-// Keep the answers of one finish for later audits (sparc_rules.hpp HostFits): the table grows to
-// keep its load factor <= 1/2, up to kHostFitsMax slots (64 MB); past that new answers are not
-// kept (audits then queue those searches again; the results are the same).
-constexpr size_t kHostFitsMin = (size_t)1 << 12, kHostFitsMax = (size_t)1 << 22;
+// Keep the answers of one finish for later audits (sparc_rules.hpp HostFits; the table and its
+// growth: sparc_tables.hpp).
 int hostfits_add(Ctx* c, const std::vector<std::pair<uint32_t, uint64_t>>& keys, const std::vector<int8_t>& res) {
     if (c->hostfits_off) return SPARC_OK;
-    const size_t need = (size_t)c->hf_used + keys.size();
-    size_t cap = c->h_hf.size();
-    if (2 * need > cap && cap < kHostFitsMax) {
-        size_t ncap = std::max(cap, kHostFitsMin);
-        while (2 * need > ncap && ncap < kHostFitsMax) ncap *= 2;
-        std::vector<uint4> t(ncap, make_uint4(0u, 0u, 0u, 0u));
-        for (const uint4& e : c->h_hf)
-            if (e.w & 2u) hostfits_insert(t, e.z, (uint64_t)e.x | ((uint64_t)e.y << 32), e.w & 1u);
-        c->h_hf.swap(t);
-        if (c->d_hf) HIPCHK(c, hipFree(c->d_hf));
-        c->d_hf = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_hf, sizeof(uint4) * ncap));
-    }
+    if (hostfits_grow(c->h_hf, (size_t)c->hf_used + keys.size())) HIPCHK(c, c->d_hf.alloc(c->h_hf.size()));
     bool added = false;
     for (size_t k = 0; k < keys.size() && 2 * ((size_t)c->hf_used + 1) <= c->h_hf.size(); ++k)
         if (hostfits_insert(c->h_hf, keys[k].first, keys[k].second, res[k] == 1 ? 1u : 0u)) {
             ++c->hf_used;
             added = true;
         }
-    if (added) HIPCHK(c, hipMemcpyAsync(c->d_hf, c->h_hf.data(), sizeof(uint4) * c->h_hf.size(), hipMemcpyHostToDevice, c->stream));
+    if (added) HIPCHK(c, hipMemcpyAsync(c->d_hf.get(), c->h_hf.data(), sizeof(uint4) * c->h_hf.size(), hipMemcpyHostToDevice, c->stream));
     return SPARC_OK;
 }
 
@@ -3488,30 +2999,26 @@ int finish_queue(Ctx* c, uint64_t cnt, uint16_t* d_bits, uint64_t* d_fit) {
     const AuditCall a = c->last_audit;
     if (a.kind == 0) return fail(c, SPARC_E_STATE, "queued exact-fit searches without a recorded audit call");
     if (!d_bits || d_bits != a.bits) return fail(c, SPARC_E_STATE, "sparc_rules_finish: not the last audit call's bits");
-    if (cnt > c->fq_cap) {
+    if (cnt > c->fq_items.size()) {
         // the queue overflowed: a larger queue, and the call again from where it started (an
         // audit is deterministic: the same searches are queued, and the memo holds final answers)
         if (a.kind == 2 && !a.snap) return fail(c, SPARC_E_STATE, "queue overflow of a rule rollout without a snapshot");
-        uint64_t cap = c->fq_cap;
+        uint64_t cap = c->fq_items.size();
         while (cap < cnt) cap *= 2;
         if (cap > kFitQueueMax) return fail(c, SPARC_E_NOMEM, "exact-fit queue past 2^28 entries in one audit call");
-        HIPCHK(c, hipFree(c->fq_items));
-        c->fq_items = nullptr;
-        c->fq_cap = 0;
-        HIPCHK(c, hipMalloc(&c->fq_items, sizeof(FitTodo) * cap));
-        c->fq_cap = cap;
+        HIPCHK(c, c->fq_items.reserve(cap));
         if (a.kind == 2 && (rc = snapshot(c, a.stats, false))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->fq_count, 0, sizeof(*c->fq_count), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->fq_count.get(), 0, sizeof(unsigned long long), c->stream));
         if ((rc = launch_rules(c, a))) return rc;
         ++c->fq_reruns;
         if ((rc = read_queue_count(c, cnt))) return rc;
-        if (cnt > c->fq_cap) return fail(c, SPARC_E_STATE, "exact-fit queue overflow on the re-run");
+        if (cnt > c->fq_items.size()) return fail(c, SPARC_E_STATE, "exact-fit queue overflow on the re-run");
     }
     std::vector<FitTodo> todo(cnt);
-    HIPCHK(c, hipMemcpy(todo.data(), c->fq_items, sizeof(FitTodo) * cnt, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(todo.data(), c->fq_items.get(), sizeof(FitTodo) * cnt, hipMemcpyDeviceToHost));
     c->fq_last = cnt;
     for (const FitTodo& it : todo)
-        if (it.pos >= a.extent || it.q >= c->num_puzzles)
+        if (it.pos >= a.extent || it.q >= c->pz.num_puzzles)
             return fail(c, SPARC_E_STATE, "exact-fit queue entry outside the last audit call");
     // each distinct (puzzle, region cells) search once, on up to 16 host threads
     std::vector<std::pair<uint32_t, uint64_t>> keys(cnt);
@@ -3519,7 +3026,7 @@ int finish_queue(Ctx* c, uint64_t cnt, uint16_t* d_bits, uint64_t* d_fit) {
     std::sort(keys.begin(), keys.end());
     keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
     std::vector<int8_t> res(keys.size(), 0);
-    parallel_for(keys.size(), [&](size_t k) { res[k] = (int8_t)host_fit(c, keys[k].first, keys[k].second); });
+    parallel_for(keys.size(), [&](size_t k) { res[k] = (int8_t)host_fit(c, c->rl, keys[k].first, keys[k].second); });
     auto fits = [&](uint32_t q, uint64_t rm) {
         const auto it = std::lower_bound(keys.begin(), keys.end(), std::make_pair(q, rm));
         return res[(size_t)(it - keys.begin())] == 1;
@@ -3539,15 +3046,13 @@ int finish_queue(Ctx* c, uint64_t cnt, uint16_t* d_bits, uint64_t* d_fit) {
         if (!ok) r.clear |= SPARC_RULE_POLY_YLOP | SPARC_RULE_ALL;
         patch.push_back(r);
     }
-    RulePatch* d_patch = nullptr;
-    HIPCHK(c, hipMalloc(&d_patch, sizeof(RulePatch) * patch.size()));
-    HIPCHK(c, hipMemcpyAsync(d_patch, patch.data(), sizeof(RulePatch) * patch.size(), hipMemcpyHostToDevice, c->stream));
-    k_rule_patch<<<grid_for(patch.size()), kBlock, 0, c->stream>>>(d_patch, (uint32_t)patch.size(), d_bits, d_fit);
+    DevBuf<RulePatch> d_patch;   // lives until the stream has run the kernel (the sync below)
+    HIPCHK(c, upload(d_patch, patch, c->stream));
+    k_rule_patch<<<grid_for(patch.size()), kBlock, 0, c->stream>>>(d_patch.get(), (uint32_t)patch.size(), d_bits, d_fit);
     rc = launch_check(c);
-    HIPCHK(c, hipMemsetAsync(c->fq_count, 0, sizeof(*c->fq_count), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->fq_count.get(), 0, sizeof(unsigned long long), c->stream));
     if (!rc) rc = hostfits_add(c, keys, res);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(d_patch));
     return rc;
 }
 }  // namespace
@@ -3562,7 +3067,7 @@ int sparc_rules_device(void* ctx, uint16_t* d_bits, uint8_t* d_region, uint64_t*
     if (!c->rules) return fail(c, SPARC_E_STATE, "sparc_load_rules has not been called");
     // a fresh queue for this call (a caller that skipped sparc_rules_finish leaves no entries that
     // name another call's outputs), and the call recorded for sparc_rules_finish
-    HIPCHK(c, hipMemsetAsync(c->fq_count, 0, sizeof(*c->fq_count), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->fq_count.get(), 0, sizeof(unsigned long long), c->stream));
     AuditCall a;
     a.kind = 1;
     a.extent = c->n;
@@ -3576,7 +3081,7 @@ int sparc_rules_device(void* ctx, uint16_t* d_bits, uint8_t* d_region, uint64_t*
 int sparc_rules_queue_stats(void* ctx, uint64_t* out) {
     Ctx* c = static_cast<Ctx*>(ctx);
     if (!c || !out) return fail(c, SPARC_E_INVALID, "null argument");
-    out[0] = c->fq_cap;
+    out[0] = c->fq_items.size();
     out[1] = c->fq_last;
     out[2] = c->fq_reruns;
     return SPARC_OK;
@@ -3643,21 +3148,21 @@ int sparc_rules_host(void* ctx, uint16_t* bits, uint8_t* region, uint64_t* fit) 
     if (rc) return rc;
     const size_t n = c->n, rb = n * 64 * c->W;
     if ((rc = audit_scratch(c))) return rc;
-    rc = sparc_rules_device(c, c->s_bits, region ? c->s_region : nullptr, fit ? c->s_fit : nullptr);
+    rc = sparc_rules_device(c, c->s_bits.get(), region ? c->s_region.get() : nullptr, fit ? c->s_fit.get() : nullptr);
     if (rc) return rc;
     // the queue count travels with the outputs: one synchronisation when nothing was queued (an
     // exact fit past the GPU's node cap is rare), else the host finishes the searches and the
     // patched bits / fit are read again
-    if (!c->h_count) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_count), sizeof(uint64_t), hipHostMallocDefault));
-    HIPCHK(c, hipMemcpyAsync(c->h_count, c->fq_count, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (bits) HIPCHK(c, hipMemcpyAsync(bits, c->s_bits, 2 * n, hipMemcpyDeviceToHost, c->stream));
-    if (region) HIPCHK(c, hipMemcpyAsync(region, c->s_region, rb, hipMemcpyDeviceToHost, c->stream));
-    if (fit) HIPCHK(c, hipMemcpyAsync(fit, c->s_fit, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, c->h_count.ensure(hipHostMallocDefault));
+    HIPCHK(c, hipMemcpyAsync(c->h_count.get(), c->fq_count.get(), sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (bits) HIPCHK(c, hipMemcpyAsync(bits, c->s_bits.get(), 2 * n, hipMemcpyDeviceToHost, c->stream));
+    if (region) HIPCHK(c, hipMemcpyAsync(region, c->s_region.get(), rb, hipMemcpyDeviceToHost, c->stream));
+    if (fit) HIPCHK(c, hipMemcpyAsync(fit, c->s_fit.get(), 8 * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint64_t cnt = *c->h_count;
-    if ((rc = finish_queue(c, cnt, c->s_bits, fit ? c->s_fit : nullptr)) || cnt == 0) return rc;
-    if (bits) HIPCHK(c, hipMemcpyAsync(bits, c->s_bits, 2 * n, hipMemcpyDeviceToHost, c->stream));
-    if (fit) HIPCHK(c, hipMemcpyAsync(fit, c->s_fit, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    const uint64_t cnt = *c->h_count.get();
+    if ((rc = finish_queue(c, cnt, c->s_bits.get(), fit ? c->s_fit.get() : nullptr)) || cnt == 0) return rc;
+    if (bits) HIPCHK(c, hipMemcpyAsync(bits, c->s_bits.get(), 2 * n, hipMemcpyDeviceToHost, c->stream));
+    if (fit) HIPCHK(c, hipMemcpyAsync(fit, c->s_fit.get(), 8 * n, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 
@@ -3672,34 +3177,31 @@ int env_call(Ctx* c, int32_t env, int32_t op, uint32_t arg, int32_t audit, sparc
     if (env < 0 || (uint32_t)env >= c->n) return fail(c, SPARC_E_INVALID, "env index out of range");
     if (op == 2 && !c->has_state && c->n != 1)
         return fail(c, SPARC_E_STATE, "first reset must cover every env (sparc_reset_*)");
-    if (op == 2 && arg >= c->num_puzzles) return fail(c, SPARC_E_INVALID, "puzzle index out of range");
+    if (op == 2 && arg >= c->pz.num_puzzles) return fail(c, SPARC_E_INVALID, "puzzle index out of range");
     if (audit && !c->rules) return fail(c, SPARC_E_STATE, "sparc_load_rules has not been called");
-    if (!c->h_rec) {
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_rec), sizeof(sparc_env_record), hipHostMallocMapped));
-        HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_rec), c->h_rec, 0));
-    }
+    HIPCHK(c, c->h_rec.ensure(hipHostMallocMapped));
     const Params p = make_params(c);
     dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
-        k_env_op<decltype(w)::value, decltype(tb)::value><<<1, 64, 0, c->stream>>>(p, (uint32_t)env, op, arg, c->d_rec);
+        k_env_op<decltype(w)::value, decltype(tb)::value><<<1, 64, 0, c->stream>>>(p, (uint32_t)env, op, arg, c->h_rec.dev());
     });
     if ((rc = launch_check(c))) return rc;
     if (op == 2) c->has_state = true;
     if (audit) {
         if ((rc = audit_scratch(c))) return rc;
-        if ((rc = sparc_rules_device(c, c->s_bits, c->s_region, c->s_fit))) return rc;
-        k_env_audit<<<1, 64, 0, c->stream>>>((uint32_t)env, (uint32_t)c->W, c->s_bits, c->s_region, c->s_fit,
-                                             c->fq_count, c->d_rec);
+        if ((rc = sparc_rules_device(c, c->s_bits.get(), c->s_region.get(), c->s_fit.get()))) return rc;
+        k_env_audit<<<1, 64, 0, c->stream>>>((uint32_t)env, (uint32_t)c->W, c->s_bits.get(), c->s_region.get(), c->s_fit.get(),
+                                             c->fq_count.get(), c->h_rec.dev());
         if ((rc = launch_check(c))) return rc;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    *out = *c->h_rec;
+    *out = *c->h_rec.get();
     if (audit) c->fq_last = 0;
     if (audit && out->host_fits) {   // exact fits past the GPU's node cap: finished on the host
         uint64_t cnt = 0;
         if ((rc = read_queue_count(c, cnt))) return rc;
-        if ((rc = finish_queue(c, cnt, c->s_bits, c->s_fit))) return rc;
-        HIPCHK(c, hipMemcpyAsync(&out->rule_bits, c->s_bits + env, 2, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&out->fit, c->s_fit + env, 8, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = finish_queue(c, cnt, c->s_bits.get(), c->s_fit.get()))) return rc;
+        HIPCHK(c, hipMemcpyAsync(&out->rule_bits, c->s_bits.get() + env, 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&out->fit, c->s_fit.get() + env, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return SPARC_OK;
@@ -3733,12 +3235,12 @@ int sparc_read_state(void* ctx, const sparc_state_host* o) {
     if (!o) return fail(c, SPARC_E_INVALID, "null argument");
     const size_t n = c->n;
     std::vector<uint32_t> pos(n), aux(n);
-    HIPCHK(c, hipMemcpyAsync(pos.data(), c->pos, 4 * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(aux.data(), c->aux, 4 * n, hipMemcpyDeviceToHost, c->stream));
-    if (o->step) HIPCHK(c, hipMemcpyAsync(o->step, c->step, 4 * n, hipMemcpyDeviceToHost, c->stream));
-    if (o->puzzle) HIPCHK(c, hipMemcpyAsync(o->puzzle, c->pid, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pos.data(), c->pos.get(), 4 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(aux.data(), c->aux.get(), 4 * n, hipMemcpyDeviceToHost, c->stream));
+    if (o->step) HIPCHK(c, hipMemcpyAsync(o->step, c->step.get(), 4 * n, hipMemcpyDeviceToHost, c->stream));
+    if (o->puzzle) HIPCHK(c, hipMemcpyAsync(o->puzzle, c->pid.get(), 4 * n, hipMemcpyDeviceToHost, c->stream));
     if (o->visited)
-        HIPCHK(c, hipMemcpyAsync(o->visited, c->vis, 8 * n * c->W, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(o->visited, c->vis.get(), 8 * n * c->W, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < n; ++i) {
         if (o->x) o->x[i] = (uint8_t)(pos[i] & 0xFF);
@@ -3761,13 +3263,13 @@ int sparc_set_visited_host(void* ctx, const uint64_t* visited) {
     // SPaRC_Gym.py:185; no pop can clear it) and nothing outside its puzzle's lattice
     const size_t n = c->n;
     std::vector<uint32_t> pid(n);
-    HIPCHK(c, hipMemcpyAsync(pid.data(), c->pid, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pid.data(), c->pid.get(), 4 * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint32_t pitch = (uint32_t)c->cfg.pitch;
     const size_t W = (size_t)c->W;
-    std::vector<uint64_t> lat(c->num_puzzles * W, 0ull);   // each puzzle's lattice points
-    for (size_t q = 0; q < c->num_puzzles; ++q) {
-        const uint32_t w0 = c->h_info[4 * q], X = w0 & 0xFFu, Y = (w0 >> 8) & 0xFFu;
+    std::vector<uint64_t> lat(c->pz.num_puzzles * W, 0ull);   // each puzzle's lattice points
+    for (size_t q = 0; q < c->pz.num_puzzles; ++q) {
+        const uint32_t w0 = c->pz.h_info[q].x, X = w0 & 0xFFu, Y = (w0 >> 8) & 0xFFu;
         for (uint32_t x = 0; x < X; ++x)
             for (uint32_t y = 0; y < Y; ++y) {
                 const uint32_t b = x * pitch + y;
@@ -3776,8 +3278,8 @@ int sparc_set_visited_host(void* ctx, const uint64_t* visited) {
     }
     for (size_t i = 0; i < n; ++i) {
         const uint32_t q = pid[i];
-        if (q >= c->num_puzzles) return fail(c, SPARC_E_STATE, "env puzzle index out of range");
-        const uint32_t w0 = c->h_info[4 * (size_t)q];
+        if (q >= c->pz.num_puzzles) return fail(c, SPARC_E_STATE, "env puzzle index out of range");
+        const uint32_t w0 = c->pz.h_info[q].x;
         const uint32_t X = w0 & 0xFFu, Y = (w0 >> 8) & 0xFFu, sb = ((w0 >> 16) & 0xFFu) * pitch + (w0 >> 24);
         for (size_t k = 0; k < W; ++k) {
             const uint64_t v = visited[k * n + i];
@@ -3792,7 +3294,7 @@ int sparc_set_visited_host(void* ctx, const uint64_t* visited) {
             }
         }
     }
-    HIPCHK(c, hipMemcpyAsync(c->vis, visited, sizeof(uint64_t) * c->W * c->n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->vis.get(), visited, sizeof(uint64_t) * c->W * c->n, hipMemcpyHostToDevice, c->stream));
     return sparc_sync(c);
 }
 
@@ -3801,12 +3303,12 @@ int sparc_state_ptr(void* ctx, int32_t which, void** d_ptr) {
     Ctx* c = static_cast<Ctx*>(ctx);
     if (!c || !d_ptr) return fail(c, SPARC_E_INVALID, "null argument");
     switch (which) {
-        case 0: *d_ptr = c->vis; break;
-        case 1: *d_ptr = c->pos; break;
-        case 2: *d_ptr = c->aux; break;
-        case 3: *d_ptr = c->step; break;
-        case 4: *d_ptr = c->pid; break;
-        case 5: *d_ptr = c->dirs; break;
+        case 0: *d_ptr = c->vis.get(); break;
+        case 1: *d_ptr = c->pos.get(); break;
+        case 2: *d_ptr = c->aux.get(); break;
+        case 3: *d_ptr = c->step.get(); break;
+        case 4: *d_ptr = c->pid.get(); break;
+        case 5: *d_ptr = c->dirs.get(); break;
         default: return fail(c, SPARC_E_INVALID, "unknown state field");
     }
     return SPARC_OK;
@@ -3843,20 +3345,8 @@ sparc_snapshot_info snapshot_info(const Ctx* c) {
     s.traceback = c->cfg.traceback;
     s.max_steps = c->cfg.max_steps;
     s.record_bytes = snap_record_bytes(c->W, c->cfg.traceback != 0);
-    s.table_hash = c->table_hash;
+    s.table_hash = c->pz.table_hash;
     return s;
-}
-
-// device scratch of at least `need` bytes (kept; replaced by a larger one on demand, as Ctx::snap)
-template <class T>
-int grow(Ctx* c, T** buf, size_t* have, size_t need) {
-    if (need <= *have) return SPARC_OK;
-    if (*buf) HIPCHK(c, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(buf), need));
-    *have = need;
-    return SPARC_OK;
 }
 
 int check_snapshot_info(Ctx* c, const sparc_snapshot_info* in) {
@@ -3956,11 +3446,11 @@ int sparc_fork_device(void* ctx, const uint32_t* d_src, const uint8_t* d_mask, u
     if (rc) return rc;
     if (!d_src) return fail(c, SPARC_E_INVALID, "null src");
     const size_t rb = (size_t)snap_record_bytes(c->W, c->cfg.traceback != 0);
-    if ((rc = grow(c, &c->fk_rec, &c->fk_rec_bytes, rb * c->n))) return rc;
+    HIPCHK(c, c->fk_rec.reserve(rb * c->n));
     // record j <- env j for every env (coalesced), then env i <- record d_src[i]: all reads of the
     // state come first, and the gather reads whole records
-    if ((rc = launch_snapshot(c, nullptr, c->n, c->fk_rec))) return rc;
-    return launch_restore(c, c->fk_rec, c->n, d_src, d_mask, d_flags);
+    if ((rc = launch_snapshot(c, nullptr, c->n, c->fk_rec.get()))) return rc;
+    return launch_restore(c, c->fk_rec.get(), c->n, d_src, d_mask, d_flags);
 }
 
 int sparc_snapshot_host(void* ctx, const uint32_t* env, int64_t M, void* records) {
@@ -3974,13 +3464,13 @@ int sparc_snapshot_host(void* ctx, const uint32_t* env, int64_t M, void* records
         for (int64_t j = 0; j < M; ++j)
             if (env[j] >= c->n) return fail(c, SPARC_E_INVALID, "env index out of range");
     const size_t bytes = (size_t)snap_record_bytes(c->W, c->cfg.traceback != 0) * (size_t)M;
-    if ((rc = grow(c, &c->fk_rec, &c->fk_rec_bytes, bytes))) return rc;
+    HIPCHK(c, c->fk_rec.reserve(bytes));
     if (env) {
-        if ((rc = grow(c, &c->fk_idx, &c->fk_idx_bytes, sizeof(uint32_t) * (size_t)M))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->fk_idx, env, sizeof(uint32_t) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, c->fk_idx.reserve((size_t)M));
+        HIPCHK(c, hipMemcpyAsync(c->fk_idx.get(), env, sizeof(uint32_t) * (size_t)M, hipMemcpyHostToDevice, c->stream));
     }
-    if ((rc = launch_snapshot(c, env ? c->fk_idx : nullptr, (uint32_t)M, c->fk_rec))) return rc;
-    HIPCHK(c, hipMemcpyAsync(records, c->fk_rec, bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = launch_snapshot(c, env ? c->fk_idx.get() : nullptr, (uint32_t)M, c->fk_rec.get()))) return rc;
+    HIPCHK(c, hipMemcpyAsync(records, c->fk_rec.get(), bytes, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 
@@ -3999,15 +3489,15 @@ int sparc_restore_host(void* ctx, const sparc_snapshot_info* info, const void* r
         for (uint32_t i = 0; i < c->n; ++i)
             if ((!mask || mask[i]) && src[i] >= (uint64_t)M) return fail(c, SPARC_E_INVALID, "record index out of range");
     const size_t bytes = (size_t)info->record_bytes * (size_t)M;
-    if ((rc = grow(c, &c->fk_rec, &c->fk_rec_bytes, bytes))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->fk_rec, records, bytes, hipMemcpyHostToDevice, c->stream));
-    if (src) HIPCHK(c, hipMemcpyAsync(c->s_pidx, src, sizeof(uint32_t) * c->n, hipMemcpyHostToDevice, c->stream));
-    if (mask) HIPCHK(c, hipMemcpyAsync(c->s_mask, mask, c->n, hipMemcpyHostToDevice, c->stream));
-    if (flags) HIPCHK(c, hipMemsetAsync(c->s_flags, 0, c->n, c->stream));
-    rc = sparc_restore_device(c, info, c->fk_rec, M, src ? c->s_pidx : nullptr, mask ? c->s_mask : nullptr,
-                              flags ? c->s_flags : nullptr);
+    HIPCHK(c, c->fk_rec.reserve(bytes));
+    HIPCHK(c, hipMemcpyAsync(c->fk_rec.get(), records, bytes, hipMemcpyHostToDevice, c->stream));
+    if (src) HIPCHK(c, hipMemcpyAsync(c->s_pidx.get(), src, sizeof(uint32_t) * c->n, hipMemcpyHostToDevice, c->stream));
+    if (mask) HIPCHK(c, hipMemcpyAsync(c->s_mask.get(), mask, c->n, hipMemcpyHostToDevice, c->stream));
+    if (flags) HIPCHK(c, hipMemsetAsync(c->s_flags.get(), 0, c->n, c->stream));
+    rc = sparc_restore_device(c, info, c->fk_rec.get(), M, src ? c->s_pidx.get() : nullptr, mask ? c->s_mask.get() : nullptr,
+                              flags ? c->s_flags.get() : nullptr);
     if (rc) return rc;
-    if (flags) HIPCHK(c, hipMemcpyAsync(flags, c->s_flags, c->n, hipMemcpyDeviceToHost, c->stream));
+    if (flags) HIPCHK(c, hipMemcpyAsync(flags, c->s_flags.get(), c->n, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 

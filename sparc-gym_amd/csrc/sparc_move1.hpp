@@ -66,7 +66,6 @@ __host__ __device__ constexpr uint32_t legal_magic(uint32_t P) {
 __host__ __device__ constexpr uint32_t window_nbm(uint32_t P) {
     return 1u | (1u << (P - 1u)) | (1u << (P + 1u)) | (1u << (2u * P));
 }
-__host__ __device__ constexpr bool split1_pitch_ok(uint32_t P) { return P >= 3u && P <= 9u; }
 
 // direction <-> window position of its neighbour (only at launch start / end)
 __device__ __forceinline__ uint32_t dir_pos1(uint32_t d, uint32_t P) {

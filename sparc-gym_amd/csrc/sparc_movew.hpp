@@ -27,18 +27,6 @@
 
 namespace sparc {
 
-// runtime layout of k_rolloutWs, computed by the host for the pool (sparc_load_puzzles)
-struct SplitGeom {
-    uint32_t P2;        // internal pitch (<= 16: the window's right neighbour is bit 2 * P2 <= 32)
-    uint32_t B;         // board dwords per lane (board + one zero dword above the top row)
-    uint32_t BS;        // B rounded up to 4: dwords per lane in LDS and per puzzle in the reset-board table
-    uint32_t M;         // move-stack bytes per lane (>= the lattice's point count, multiple of 16:
-                        // a step writes slot len - 1 even when it does not move, and len <= points)
-    uint32_t nbr_pos;   // window bit of each direction's neighbour, one byte per direction
-    uint32_t pair;      // LDS bytes per move / trie wave pair
-    uint32_t off_board, off_stack;   // their offsets within a pair
-};
-
 // 16-bit hand-over word of the multi-word kernel: bits 0-7 the flag byte, bits 8-9
 // fwd - pop + 1, bits 10-11 action & 3.  The trie wave widens it to TrieLane's word (flag byte
 // | (fwd - pop) << 16) and the action.
@@ -48,8 +36,6 @@ __device__ __forceinline__ uint32_t hand_word16(uint32_t a, uint32_t fwd, uint32
 __device__ __forceinline__ uint32_t widen_hand_word(uint32_t h) {
     return (h & 0xFFu) | ((__builtin_amdgcn_ubfe(h, 8u, 2u) - 1u) << 16);
 }
-
-constexpr uint32_t kBoardRegs = 4;   // 16-B pieces of the next reset board kept in registers
 
 template <bool TB>
 struct MoveLaneW {

@@ -35,28 +35,8 @@
 namespace sparc {
 
 constexpr uint32_t kErrRuleTable = 8, kErrJoin = 16;   // Params::err bits (sparc_sync)
-// rule-plane indices of include/sparc_gym_amd.h (SPARC_RULE_PLANES), then the planes the loader
-// (sparc_load_rules) derives from the instance list for the device copy: the net instance area
-// of each cell (Σ poly areas − Σ ylop areas of the instances there, 8-bit two's complement,
-// bit-sliced), so a region's area check (_polyfit_check_area 700-709) is 8 popcounts instead of
-// a walk over the puzzle's instance list with two dependent loads per instance.  RP_INST of the
-// device copy is rewritten from the list too (cells holding an instance).
-enum : uint32_t {
-    RP_CELLS = 0, RP_LATTICE, RP_GAPS, RP_DOTS, RP_TRI, RP_TRI0, RP_TRI1, RP_TRI2, RP_STAR, RP_SQUARE,
-    RP_COLORED, RP_COL1, RP_M0 = RP_COL1 + 8, RP_M1, RP_M2, RP_NOTFIRST, RP_NOTLAST, RP_INST, RP_ABI,
-    RP_AREA0 = RP_ABI, RP_COUNT = RP_AREA0 + 8
-};
-constexpr int kAreaPlanes = 8;
 constexpr int kFitCells = 64;     // cell grid of the exact fit (15 x 15 lattice: 7 x 7 = 49)
-// The GPU's search keeps its per-region lists in registers / scratch of these sizes; a puzzle with
-// more ylops or distinct poly shapes (instances sit at cell centres, one per cell, so never more
-// than 64 of either) is flagged by the loader (kHostFit) and its searches run on the host
-// (exact_fit<..., kHostFitMax, kHostFitMax, kHostFitPlanes>, sparc_kernels.hip host_fit)
-constexpr int kFitYlops = 16;
-constexpr int kFitShapes = 16;
 constexpr int kFitDepth = 64;
-constexpr int kHostFitMax = 64, kHostFitPlanes = 8;   // every valid puzzle: <= 64 cells, counts >= -65
-constexpr uint32_t kHostFit = 0x80000000u;            // instance count flag: searches on the host
 // default node cap of one exact-fit search on the GPU (sparc_set_fit_cap): a search that passes it
 // stops, and the host finishes it without a cap (FitQueue below, the C ABI's fallback), so
 // callers see the reference's unbounded answer
@@ -90,11 +70,6 @@ struct HostFits {
     uint32_t mask;   // slots - 1 (a power of two)
     uint32_t used;
 };
-__host__ __device__ __forceinline__ uint32_t hostfit_slot(uint32_t q, uint64_t rm, uint32_t mask) {
-    uint64_t h = rm * 0x9E3779B97F4A7C15ull ^ ((uint64_t)q * 0xC2B2AE3D27D4EB4Full);
-    h ^= h >> 29;
-    return (uint32_t)h & mask;
-}
 // 1 / 0: the host's answer, -1: not finished on the host
 __device__ __forceinline__ int hostfit_find(const HostFits& hf, uint32_t q, uint64_t rm) {
     if (hf.used == 0) return -1;
@@ -129,10 +104,6 @@ struct RulesTab {
     // (W = 1: 96 B; the planes alone are spread over 264 B of the plane table)
     const uint64_t* __restrict__ rows;
 };
-template <int W>
-__host__ __device__ constexpr uint32_t rule_row_u64() { return 10u * W + 2u; }
-constexpr uint32_t kNoRegTab = 0xFFFFFFFFu;
-constexpr uint32_t kRegTabCells = 12;
 
 template <int W>
 struct BB {
@@ -535,8 +506,6 @@ struct PuzzleRules {
     uint32_t tbit;  // the target's board bit tx * pitch + ty
     FitIn fin;
 };
-constexpr uint32_t kBasePlanes[10] = {RP_CELLS, RP_LATTICE, RP_GAPS, RP_DOTS, RP_TRI, RP_TRI0, RP_TRI1, RP_TRI2,
-                                      RP_NOTFIRST, RP_NOTLAST};
 enum : uint32_t { kB_CELLS = 0, kB_LATTICE, kB_GAPS, kB_DOTS, kB_TRI, kB_TRI0, kB_TRI1, kB_TRI2, kB_NOTFIRST, kB_NOTLAST };
 template <int W>
 __device__ __forceinline__ PuzzleRules<W> puzzle_rules(const Params& p, const RulesTab& rt, uint32_t q) {

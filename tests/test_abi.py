@@ -89,6 +89,8 @@ def test_no_environment_variable_selects_a_kernel():
     assert not imported & {"getenv", "secure_getenv", "__secure_getenv"}, imported & {"getenv", "secure_getenv"}
     lib = _lib.load()
     assert lib.sparc_set_variant(None, 1, 1) == -1
-    src = open(os.path.join(REPO, "sparc-gym_amd", "csrc", "sparc_kernels.hip")).read()
+    csrc = os.path.join(REPO, "sparc-gym_amd", "csrc")
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)))
+    assert "sparc_load_puzzles" in src and "build_puzzle_tables" in src
     for name in ("SPARC_IO_CODES", "SPARC_RULE_ROLLOUT", "SPARC_R1R_SHAPE"):
         assert f'"{name}"' not in src

@@ -111,7 +111,7 @@ VARIANTS = {
         __builtin_amdgcn_s_setprio(1);
         MoveLane1<TB> m;""")],
     # the split tables without the 128-B line alignment of each puzzle's trie records
-    "noalign": [("sparc_kernels.hip", "            nn8 = (nn8 + 15u) & ~(size_t)15u;\n", "")],
+    "noalign": [("sparc_tables.hpp", "            nn8 = (nn8 + 15u) & ~(size_t)15u;\n", "")],
     # k_rollout1s: the move and trie waves read a whole 16-step tile's inputs at once
     "group16": [("sparc_kernels.hip", "constexpr int kGroup1s = 4;", "constexpr int kGroup1s = 16;")],
     "group8": [("sparc_kernels.hip", "constexpr int kGroup1s = 4;", "constexpr int kGroup1s = 8;")],

@@ -167,8 +167,8 @@ extern "C" int sparc_diag_rollout1s(void* ctx, int32_t T, const uint8_t* d_act, 
     const Params p = make_params(c);
     if (!split1_pitch_ok(p.pitch)) return fail(c, SPARC_E_INVALID, "diag: pitch outside 3..9");
     // pools past the LDS row budget: the global-row kernel (row slots), product waves only
-    const bool lds = kS_Base + split_table_bytes(c->num_puzzles) <= kMaxDynLds;
-    const size_t shm = kS_Base + (lds ? split_table_bytes(c->num_puzzles) : kS_SlotBytes);
+    const bool lds = kS_Base + split_table_bytes(c->pz.num_puzzles) <= kMaxDynLds;
+    const size_t shm = kS_Base + (lds ? split_table_bytes(c->pz.num_puzzles) : kS_SlotBytes);
     if (!lds && variant != 0) return fail(c, SPARC_E_INVALID, "diag: global-row pools run variant 0 only");
     auto go = [&](auto kern) {
         rc = allow_big_lds(c, reinterpret_cast<const void*>(kern));
