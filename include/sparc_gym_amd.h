@@ -316,6 +316,42 @@ int sparc_snapshot_host(void *ctx, const uint32_t *env, int64_t M, void *records
 int sparc_restore_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
                        const uint32_t *src, const uint8_t *mask, uint8_t *flags);
 
+/* ---- one-ply expansion of records: the successor function of a tree search ---------------------
+ * A search holds a frontier of positions whose size changes at every level, not "N envs".  This
+ * call takes M records (any M >= 1 with 4 * M < 2^31, independent of num_envs) and writes all four
+ * successors of each, in one launch and without touching an env: the context supplies its puzzle
+ * table, words, pitch, traceback, max_steps and autoreset mode only, its env state is neither
+ * read nor written, and sparc_load_puzzles is enough (no reset needed).
+ *  d_children     [M][4] records, M * 4 * record_bytes bytes.  Child (j, a) is byte for byte the
+ *                 record sparc_snapshot_device gives for an env restored from record j in this
+ *                 context (sparc_restore_device) and stepped once with action a by
+ *                 sparc_step_device (step, SPaRC_Gym.py:1111-1238), under the context's max_steps
+ *                 and autoreset mode.  Nothing is special-cased, so:
+ *                  - an illegal a (not in _get_legal_actions, 1024-1051) gives the no-move state
+ *                    with step + 1 (and its truncation, if that reaches max_steps);
+ *                  - under SPARC_AUTORESET_NEXT_STEP a pending parent (one whose last step ended
+ *                    its episode) gives four identical children: the reset state of the next
+ *                    puzzle, flags bit 6 set, code 0;
+ *                  - under SPARC_AUTORESET_NONE a pending parent steps past the end as the
+ *                    reference does.
+ *  d_reward       [M][4] int8, d_flags [M][4] uint8: the reward code and the flag byte of those
+ *                 steps, as sparc_step_device writes them.
+ *  d_parent_flags [M] uint8: the legal actions of the PARENT state in bits 2-5 (1024-1051), as
+ *                 the d_flags of sparc_restore_device: which children are real moves.
+ * Every output but d_children may be NULL.  info must match the context as for a restore
+ * (SPARC_E_INVALID naming the field); d_records and d_children must be non-NULL and 16-B aligned.
+ * Every parent is checked on the device before anything is indexed with it, with the conditions of
+ * sparc_restore_device.  A parent that fails gets four zeroed children (which no restore or expand
+ * accepts), code 0, flags 0 and parent flags 0, and sparc_sync reports the error; every other
+ * parent is unaffected.  Records this call wrote are valid parents.  Device pointers,
+ * asynchronous. */
+int sparc_expand_device(void *ctx, const sparc_snapshot_info *info, const void *d_records, int64_t M,
+                        void *d_children, int8_t *d_reward, uint8_t *d_flags, uint8_t *d_parent_flags);
+/* the host-pointer form: staged through the context's stream, returns after the data have moved
+ * (no alignment requirement) */
+int sparc_expand_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
+                      void *children, int8_t *reward, uint8_t *flags, uint8_t *parent_flags);
+
 /* ---- rule audit: info['rule_status'] (_validate_rules, SPaRC_Gym.py:941-950) ----------------
  * Rule table, packed by sparc_gym_amd/puzzles.py:pack_rules from the processed puzzles, on the
  * step table's geometry (bit x*pitch + y, `words` u64 per board).

@@ -30,6 +30,7 @@
 #include "sparc_move1.hpp"
 #include "sparc_rules.hpp"
 #include "sparc_snapshot.hpp"
+#include "sparc_expand.hpp"
 #include "sparc_devbuf.hpp"
 #include "sparc_tables.hpp"
 #include "sparc_gym_amd.h"
@@ -2028,6 +2029,8 @@ struct Ctx {
     // (fork, the *_host forms) and an index list
     DevBuf<uint8_t> fk_rec;
     DevBuf<uint32_t> fk_idx;
+    // sparc_expand_host (sparc_expand.hpp): the children, and reward [4M] | flags [4M] | parent flags [M]
+    DevBuf<uint8_t> ex_child, ex_out;
     DevBuf<uint16_t> s_bits;        // per-env audit outputs of the host-pointer / one-env calls
     DevBuf<uint8_t> s_region;
     DevBuf<uint64_t> s_fit;
@@ -2303,7 +2306,9 @@ int sparc_sync(void* ctx) {
         if (e & 8) return fail(c, SPARC_E_STATE, "rule audit: env puzzle index outside the rule table");
         if (e & kErrJoin) return fail(c, SPARC_E_STATE, "rule rollout: an audit wave pair did not join (outputs unreliable)");
         if (e & kErrSnapshot)
-            return fail(c, SPARC_E_INVALID, "snapshot / restore / fork: index or record out of range (those envs unchanged)");
+            return fail(c, SPARC_E_INVALID,
+                        "snapshot / restore / fork / expand: index or record out of range (those envs unchanged, "
+                        "the children of those parents zeroed)");
         return fail(c, SPARC_E_INVALID, "device-side puzzle index out of range in a reset");
     }
     return SPARC_OK;
@@ -3498,6 +3503,60 @@ int sparc_restore_host(void* ctx, const sparc_snapshot_info* info, const void* r
                               flags ? c->s_flags.get() : nullptr);
     if (rc) return rc;
     if (flags) HIPCHK(c, hipMemcpyAsync(flags, c->s_flags.get(), c->n, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
+}
+
+// ---- one-ply expansion of records (sparc_expand.hpp): reads the context's tables only
+static int check_expand_args(Ctx* c, const sparc_snapshot_info* info, const void* records, int64_t M,
+                             const void* children, bool device) {
+    int rc = check_snapshot_info(c, info);
+    if (rc) return rc;
+    if (!records) return fail(c, SPARC_E_INVALID, "null records");
+    if (!children) return fail(c, SPARC_E_INVALID, "null children");
+    if (device && ((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(children)) & 15u))
+        return fail(c, SPARC_E_INVALID, "records and children must be 16-B aligned");
+    if (M < 1 || 4 * (uint64_t)M > 0x7FFFFFFFull)
+        return fail(c, SPARC_E_INVALID, "M must be at least 1 with 4 * M below 2^31");
+    return SPARC_OK;
+}
+
+int sparc_expand_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M,
+                        void* d_children, int8_t* d_reward, uint8_t* d_flags, uint8_t* d_parent_flags) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_expand_args(c, info, d_records, M, d_children, true))) return rc;
+    const Params p = make_params(c);
+    const uint32_t M4 = 4u * (uint32_t)M;
+    dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
+        k_expand<decltype(w)::value, decltype(tb)::value><<<grid_for(M4), kSnapBlock, 0, c->stream>>>(
+            p, static_cast<const uint4*>(d_records), M4, static_cast<uint4*>(d_children), d_reward, d_flags,
+            d_parent_flags);
+    });
+    return launch_check(c);
+}
+
+int sparc_expand_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M, void* children,
+                      int8_t* reward, uint8_t* flags, uint8_t* parent_flags) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_expand_args(c, info, records, M, children, false))) return rc;
+    const size_t m = (size_t)M, bytes = (size_t)info->record_bytes * m;
+    HIPCHK(c, c->fk_rec.reserve(bytes));
+    HIPCHK(c, c->ex_child.reserve(4 * bytes));
+    HIPCHK(c, c->ex_out.reserve(9 * m));
+    uint8_t* o = c->ex_out.get();
+    HIPCHK(c, hipMemcpyAsync(c->fk_rec.get(), records, bytes, hipMemcpyHostToDevice, c->stream));
+    rc = sparc_expand_device(c, info, c->fk_rec.get(), M, c->ex_child.get(), reinterpret_cast<int8_t*>(o), o + 4 * m,
+                             o + 8 * m);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(children, c->ex_child.get(), 4 * bytes, hipMemcpyDeviceToHost, c->stream));
+    if (reward) HIPCHK(c, hipMemcpyAsync(reward, o, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    if (flags) HIPCHK(c, hipMemcpyAsync(flags, o + 4 * m, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    if (parent_flags) HIPCHK(c, hipMemcpyAsync(parent_flags, o + 8 * m, m, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 

@@ -105,6 +105,10 @@ _SIGS = {
     "sparc_snapshot_host": ([c_void_p, c_void_p, ctypes.c_int64, c_void_p], c_int32),
     "sparc_restore_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_void_p,
                             c_void_p, c_void_p], c_int32),
+    "sparc_expand_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_void_p,
+                             c_void_p, c_void_p, c_void_p], c_int32),
+    "sparc_expand_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_void_p,
+                           c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_load_rules": ([c_void_p, ctypes.POINTER(SparcRulesTable)], c_int32),
     "sparc_rules_device": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_rules_host": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),

@@ -278,6 +278,26 @@ class SparcCore:
         self.has_state = True
         return flags
 
+    # ---------------------------------------------------------------- one-ply expansion of records
+    def expand_device(self, info, d_records, M, d_children, d_reward=None, d_flags=None, d_parent_flags=None):
+        """sparc_expand_device: children [M][4] records, reward codes / flags [M][4], the parents'
+        legal actions << 2 [M]; reads the context's tables only (asynchronous)."""
+        self._check(self.lib.sparc_expand_device(self.ctx, ctypes.byref(info), d_records, int(M), d_children,
+                                                 d_reward, d_flags, d_parent_flags))
+
+    def expand_host(self, info, records):
+        """Expand host records [M, record_bytes]: (children [4M, record_bytes] uint8, reward codes
+        [M, 4] int8, flags [M, 4] uint8, parent flags [M] uint8) on the host (synchronous)."""
+        rec = np.ascontiguousarray(records, np.uint8)
+        if rec.ndim != 2 or rec.shape[1] != info.record_bytes or len(rec) < 1:
+            raise ValueError(f"records must be [M, {info.record_bytes}] uint8 with M >= 1")
+        M = len(rec)
+        children = np.empty((4 * M, rec.shape[1]), np.uint8)
+        rew, flags, pflags = np.empty((M, 4), np.int8), np.empty((M, 4), np.uint8), np.empty(M, np.uint8)
+        self._check(self.lib.sparc_expand_host(self.ctx, ctypes.byref(info), _ptr(rec), M, _ptr(children), _ptr(rew),
+                                               _ptr(flags), _ptr(pflags)))
+        return children, rew, flags, pflags
+
 
 def visited_planes(bits, table: PuzzleTable, x_dim=None, y_dim=None):
     """Decode visited bitboards [words][N] into int32 planes [N][x_dim][y_dim] (host)."""

@@ -1,0 +1,121 @@
+"""Tree search helpers on top of ``SPaRCVecEnv.expand``: a frontier of positions is a ``Snapshot``
+(one record per node, any number of them), and one level of a search is one ``expand`` launch
+plus a compaction of the children worth keeping.
+
+The rule both helpers follow is the reference's own: a state that is done (terminated or
+truncated, step(), SPaRC_Gym.py:1192-1199) has no successors, and the successors of a live state
+are its legal actions (_get_legal_actions, 1024-1051).  Illegal actions, which ``expand`` also
+steps (the no-move state with step + 1), are dropped here.
+
+The compaction is plain torch indexing on the GPU (``nonzero`` + a row gather); its order is the
+ascending child index, parent-major then action, so every result is deterministic.  Not done
+here: detecting the same position reached twice within a frontier, and compaction inside the
+kernel.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+DONE_BITS = 3   # flags bit 0 terminated, bit 1 truncated
+
+
+def _done_mask(done, M, device):
+    """[M] bool from a bool mask, 0/1 bytes or step flags (bits 0-1)."""
+    d = torch.as_tensor(np.asarray(done) if not isinstance(done, torch.Tensor) else done, device=device)
+    if d.shape != (M,):
+        raise ValueError(f"done must have shape ({M},)")
+    if d.dtype == torch.bool:
+        return d
+    if d.dtype.is_floating_point:
+        raise ValueError("done must be a bool mask or flag bytes")
+    return (d.to(torch.int64) & DONE_BITS) != 0
+
+
+def expand_frontier(vec, snap, done=None):
+    """Expand ``snap`` once and keep only the children that are real moves of a live parent:
+    child ``(j, a)`` stays iff bit ``a`` of parent ``j``'s legal mask is set and ``done[j]`` is
+    not.  ``done``: [M] bool, or the flag bytes the parents were produced with (bits 0-1:
+    terminated, truncated); default: every parent is live.  Returns a dict: ``children`` (a
+    ``Snapshot`` of the K kept records, on the GPU), ``parent`` [K] int64 (row of ``snap``),
+    ``action`` [K] int64, ``reward_code`` [K] int8, ``flags`` [K] uint8, in ascending
+    ``4 * parent + action``.  ``flags`` are the done bits for the next level."""
+    out = vec.expand(snap)
+    M = len(snap)
+    legal = out["legal_mask"].to(torch.int64)
+    keep = ((legal[:, None] >> torch.arange(4, device=legal.device)) & 1) != 0
+    if done is not None:
+        keep &= ~_done_mask(done, M, legal.device)[:, None]
+    idx = keep.reshape(-1).nonzero().squeeze(1)          # ascending child index
+    return {"children": out["children"].select(idx), "parent": idx >> 2, "action": idx & 3,
+            "reward_code": out["reward_code"].reshape(-1)[idx], "flags": out["flags"].reshape(-1)[idx]}
+
+
+def enumerate_paths(vec, puzzle_indices, max_depth=None, max_frontier=1 << 22):
+    """Level-synchronous breadth-first expansion of the legal-move trees of ``puzzle_indices``
+    (one root per entry: that puzzle's reset state), all roots at once.  A node is expanded iff
+    it is not done; its children are its legal actions.  Stops after ``max_depth`` levels or when
+    no live node is left, and raises RuntimeError if a level holds more than ``max_frontier``
+    nodes.  With traceback every move can be undone, so the tree ends only through
+    ``max_steps``: give ``max_depth``.
+
+    The roots come from ``vec.reset`` and ``vec.snapshot``, so ``vec`` needs at least
+    ``len(puzzle_indices)`` envs and its state is overwritten.
+
+    Returns a dict of int64 arrays [R, D + 1] (D: the deepest level reached; column 0 is the
+    roots): ``nodes`` the nodes at each depth, ``solved`` those that ended with reward code +100,
+    ``ended`` those that ended otherwise (terminated or truncated); and ``solution``: per root,
+    the actions of one path to a +100 node (the shallowest, lowest-index one) or None."""
+    q = np.asarray(puzzle_indices, np.int64)
+    R = len(q)
+    if q.ndim != 1 or R < 1 or R > vec.num_envs:
+        raise ValueError(f"puzzle_indices must hold 1..{vec.num_envs} puzzle indices")
+    full = np.full(vec.num_envs, q[0], np.int64)
+    full[:R] = q
+    vec.reset(options={"puzzle_index": full})
+    frontier = vec.snapshot(envs=np.arange(R))
+    dev = frontier.records.device
+    root = torch.arange(R, device=dev)
+    nodes, solved, ended = [np.ones(R, np.int64)], [np.zeros(R, np.int64)], [np.zeros(R, np.int64)]
+    levels = []                                          # per level: parent, action, live rows
+    found = {}                                           # root -> (level, row) of its first +100 node
+    depth = 0
+    while len(frontier) and (max_depth is None or depth < max_depth):
+        out = expand_frontier(vec, frontier)             # the frontier holds live nodes only
+        K = len(out["children"])
+        if K == 0:                                       # roots without a legal move
+            break
+        if K > max_frontier:
+            raise RuntimeError(f"depth {depth + 1} holds {K} nodes, more than max_frontier = {max_frontier}")
+        depth += 1
+        croot = root[out["parent"]]
+        done = (out["flags"] & DONE_BITS) != 0
+        win = out["reward_code"] == 100
+        count = lambda m: torch.bincount(croot[m], minlength=R).cpu().numpy().astype(np.int64)  # noqa: E731
+        nodes.append(torch.bincount(croot, minlength=R).cpu().numpy().astype(np.int64))
+        solved.append(count(done & win))
+        ended.append(count(done & ~win))
+        rows = (done & win).nonzero().squeeze(1)
+        if len(rows):
+            rows_h = rows.cpu().numpy()
+            for r, k in zip(*np.unique(croot[rows].cpu().numpy(), return_index=True)):
+                found.setdefault(int(r), (depth, int(rows_h[k])))
+        # the live nodes are the next frontier; a level keeps, for the walk back to the root, its
+        # nodes' parent (a row of the frontier it was expanded from) and action, and the level
+        # rows that became the next frontier
+        live = (~done).nonzero().squeeze(1)
+        levels.append((out["parent"].cpu().numpy(), out["action"].cpu().numpy(), live.cpu().numpy()))
+        frontier = out["children"].select(live)
+        root = croot[live]
+    solution = [None] * R
+    for r, (d, row) in found.items():
+        acts = []
+        while d >= 1:
+            parent, action, _ = levels[d - 1]
+            acts.append(int(action[row]))
+            prow = int(parent[row])                      # a row of the frontier expanded at level d
+            row = prow if d == 1 else int(levels[d - 2][2][prow])
+            d -= 1
+        solution[r] = acts[::-1]
+    return {"nodes": np.stack(nodes, 1), "solved": np.stack(solved, 1), "ended": np.stack(ended, 1),
+            "solution": solution}

@@ -92,6 +92,46 @@ class Snapshot:
             r = torch.from_numpy(np.ascontiguousarray(r, np.uint8))
         return Snapshot(r.to(device), self.info)
 
+    # ------------------------------------------------------------------ frontiers
+    def select(self, idx):
+        """A new ``Snapshot`` of rows ``idx``: a tensor, array or list of integers (any order,
+        repeats allowed) or a bool mask over the records.  Stays where the records are."""
+        r = self.records
+        if isinstance(r, np.ndarray):
+            i = idx.detach().cpu().numpy() if hasattr(idx, "detach") else np.asarray(idx)
+            if i.dtype != np.bool_ and i.dtype.kind not in "iu":
+                raise ValueError("idx must hold integers or be a bool mask")
+            if i.ndim != 1 or (i.dtype == np.bool_ and len(i) != len(r)):
+                raise ValueError("idx must be one-dimensional (a mask: one entry per record)")
+            return Snapshot(np.ascontiguousarray(r[i]), self.info)
+        import torch
+        i = torch.as_tensor(idx, device=r.device)
+        if i.dtype.is_floating_point or i.dtype.is_complex:
+            raise ValueError("idx must hold integers or be a bool mask")
+        if i.ndim != 1 or (i.dtype == torch.bool and len(i) != len(r)):
+            raise ValueError("idx must be one-dimensional (a mask: one entry per record)")
+        if i.dtype not in (torch.bool, torch.int64):
+            i = i.to(torch.int64)
+        return Snapshot(r[i].contiguous(), self.info)
+
+    @classmethod
+    def cat(cls, snaps):
+        """The records of ``snaps`` in order, as one ``Snapshot``.  ValueError naming the field if
+        their headers differ; on the GPU if the first one's records are (the others are moved)."""
+        snaps = list(snaps)
+        if not snaps:
+            raise ValueError("nothing to concatenate")
+        first = snaps[0]
+        for s in snaps[1:]:
+            bad = info_mismatch(first.info, s.info)
+            if bad is not None:
+                raise ValueError(f"snapshots do not match: {bad} differs")
+        if isinstance(first.records, np.ndarray):
+            return cls(np.concatenate([s.numpy() for s in snaps]), first.info)
+        import torch
+        dev = first.records.device
+        return cls(torch.cat([s.to(dev).records for s in snaps]), first.info)
+
     # ------------------------------------------------------------------ file
     def save(self, path):
         rec = self.numpy()

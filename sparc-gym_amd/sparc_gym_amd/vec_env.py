@@ -30,6 +30,8 @@ Snapshot / restore / fork: ``snapshot()`` returns the state of any envs as opaqu
 (``sparc_gym_amd.Snapshot``), ``restore(snap, src, mask)`` writes record ``src[i]`` into env ``i``
 of any env on the same puzzle table, ``fork(src)`` makes env ``i`` a copy of env ``src[i]``: one
 position fanned out to every env for playouts, beam search or MCTS, or a run saved and resumed.
+``expand(snap)`` returns all four successors of any number of records in one launch without
+touching an env (the one-ply step of a tree search; ``sparc_gym_amd.search`` builds on it).
 """
 from __future__ import annotations
 
@@ -497,6 +499,41 @@ class SPaRCVecEnv:
         flags = torch.zeros(n, dtype=torch.uint8, device=self.device)
         self.core.fork_device(idx.data_ptr(), None if m is None else m.data_ptr(), flags.data_ptr())
         return self._restored(flags, m)
+
+    def expand(self, snap=None, envs=None):
+        """All four successors of every record of ``snap`` (default: ``self.snapshot(envs)``), in
+        one launch and without changing any env: the one-ply step of a tree search over a
+        frontier of any size.  Returns a dict: ``children`` a ``Snapshot`` of ``4 * M`` records
+        on the GPU, child ``(j, a)`` at row ``4 * j + a``, byte for byte what ``restore`` of
+        record ``j``, one ``step`` with action ``a`` and ``snapshot`` give under this env's
+        ``max_steps`` and ``autoreset`` (an illegal ``a``: the no-move state with step + 1; a
+        pending parent under next-step autoreset: four identical reset children, flag 64);
+        ``reward_code`` [M, 4] int8 and ``flags`` [M, 4] uint8 of those steps; ``legal_mask`` [M]
+        uint8, bits 0-3: the parents' legal actions, as ``info['legal_mask']``.  ValueError
+        naming the field when the snapshot's header does not match this env, as ``restore``."""
+        from .snapshot import Snapshot, info_mismatch
+        self._stream()
+        if snap is None:
+            snap = self.snapshot(envs)
+        elif envs is not None:
+            raise ValueError("give snap or envs, not both")
+        bad = info_mismatch(snap.info, self.core.snapshot_info())
+        if bad is not None:
+            raise ValueError(f"snapshot does not match this env: {bad} differs")
+        M = len(snap)
+        if M < 1 or 4 * M >= 2**31:
+            raise ValueError("a snapshot of 1 .. 2^29 - 1 records is needed")
+        rec = snap.records
+        if not isinstance(rec, torch.Tensor):
+            rec = torch.from_numpy(np.ascontiguousarray(rec, np.uint8))
+        rec = rec.to(self.device).contiguous()
+        children = torch.empty((4 * M, snap.info.record_bytes), dtype=torch.uint8, device=self.device)
+        out = torch.empty(9 * M, dtype=torch.uint8, device=self.device)   # codes | flags | parent flags
+        code, flags, pflags = out[:4 * M].view(torch.int8).view(M, 4), out[4 * M:8 * M].view(M, 4), out[8 * M:]
+        self.core.expand_device(snap.info, rec.data_ptr(), M, children.data_ptr(), code.data_ptr(), flags.data_ptr(),
+                                pflags.data_ptr())
+        return {"children": Snapshot(children, snap.info), "reward_code": code, "flags": flags,
+                "legal_mask": (pflags >> 2) & 0xF}
 
     def state(self):
         """Host snapshot of the per-env state (x, y, path_len, step, puzzle, outcome, visited bits)."""
