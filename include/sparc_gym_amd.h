@@ -410,8 +410,33 @@ int sparc_load_rules(void *ctx, const sparc_rules_table *table);
 int sparc_rules_device(void *ctx, uint16_t *d_bits, uint8_t *d_region, uint64_t *d_fit);
 int sparc_rules_host(void *ctx, uint16_t *bits, uint8_t *region, uint64_t *fit);
 
+/* Audit M state records (sparc_snapshot_device / sparc_expand_device; M >= 1, M < 2^31, M need not
+ * be num_envs): record j gets the bits, region row and fit mask that sparc_rules_device gives an
+ * env restored from it (_validate_rules, SPaRC_Gym.py:941-950), in one launch and without an env.
+ * The context supplies its tables only: no env state and no per-env audit memo is read or
+ * written, so sparc_load_puzzles + sparc_load_rules are enough and no reset is needed
+ * (SPARC_E_STATE without rules loaded).
+ *  d_bits    [M] (SPARC_RULE_*), must be non-NULL
+ *  d_region  [M][64*words], d_fit [M]: as sparc_rules_device's; either may be NULL.  With both
+ *            NULL, a one-word pool whose every puzzle has a region-code table is audited by the
+ *            table-only kernel (no exact-fit search compiled in); the answers are the same.
+ * info must match the context as for a restore or an expand (SPARC_E_INVALID naming the field);
+ * d_records must be non-NULL and 16-B aligned.  Every record is checked on the device before
+ * anything is indexed with it, with the conditions of sparc_restore_device and the rule table's
+ * puzzle count.  A record that fails gets bits 0 and fit 0, its region row stays all 0xFF, and
+ * sparc_sync reports the error; every other record is unaffected.
+ * sparc_rules_finish finishes this call like the other audit calls, with d_bits and d_fit; the
+ * records may not change before it has returned (a call that queued more searches than the queue
+ * holds is run again from the same records on a larger queue).  Device pointers, asynchronous. */
+int sparc_rules_records_device(void *ctx, const sparc_snapshot_info *info, const void *d_records, int64_t M,
+                               uint16_t *d_bits, uint8_t *d_region, uint64_t *d_fit);
+/* the host-pointer form: staged through the context's stream, runs sparc_rules_finish itself and
+ * returns final bits after the data have moved, as sparc_rules_host (no alignment requirement) */
+int sparc_rules_records_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
+                             uint16_t *bits, uint8_t *region, uint64_t *fit);
+
 /* Finish the exact-fit searches that passed the GPU's node cap (or belong to a puzzle whose
- * searches run on the host) in the LAST audit call (sparc_rules_device, or
+ * searches run on the host) in the LAST audit call (sparc_rules_device, sparc_rules_records_device, or
  * sparc_rollout_rules_device: its d_rule_bits) on the host, without a cap, and patch that call's
  * outputs on the device: SPARC_RULE_SEARCH_EXHAUSTED cleared, POLY_YLOP and ALL cleared when a
  * region does not fit, and (d_fit, may be NULL) the fit bits of the regions that do.  Call it

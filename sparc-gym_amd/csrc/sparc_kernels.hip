@@ -9,6 +9,7 @@
 //   k_obs_pack dense int32 visited / agent_location planes         (_get_obs, SPaRC_Gym.py:979)
 //   k_rules    rule audit of the current state                      (_validate_rules, 941-950)
 //   k_snapshot / k_restore  the state as per-env records and back  (sparc_snapshot.hpp)
+//   k_rules_rec  rule audit of state records, without an env      (sparc_rules_rec.hpp)
 // No MFMA: this is integer / bitboard work, bound by latency and HBM.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -31,6 +32,7 @@
 #include "sparc_rules.hpp"
 #include "sparc_snapshot.hpp"
 #include "sparc_expand.hpp"
+#include "sparc_rules_rec.hpp"
 #include "sparc_devbuf.hpp"
 #include "sparc_tables.hpp"
 #include "sparc_gym_amd.h"
@@ -1919,10 +1921,11 @@ __global__ void __launch_bounds__(kBlock) k_rule_patch(const RulePatch* __restri
 
 // ------------------------------------------------------------------------------ host side
 // The last audit call that may queue exact-fit searches (sparc_rules_finish): its outputs and
-// extent (entries: N, or T * N), and for a generic rule rollout its launch, so that a call whose
-// queue overflowed runs again on a larger queue from the state it started from (Ctx::snap).
+// extent (entries: N, T * N, or M records), and for a generic rule rollout its launch, so that a
+// call whose queue overflowed runs again on a larger queue from the state it started from
+// (Ctx::snap).  A records audit runs again from the caller's records (rec, rec_pieces, extent).
 struct AuditCall {
-    int kind = 0;   // 0 none, 1 sparc_rules_device, 2 rule rollout
+    int kind = 0;   // 0 none, 1 sparc_rules_device, 2 rule rollout, 3 sparc_rules_records_device
     bool snap = false;   // kind 2: the generic rule kernel ran it from a snapshot (re-runnable)
     uint64_t extent = 0;
     uint16_t* bits = nullptr;
@@ -1934,6 +1937,8 @@ struct AuditCall {
     int8_t* rew = nullptr;
     uint8_t* flags = nullptr;
     int32_t* stats = nullptr;
+    const void* rec = nullptr;   // kind 3: the records (the caller's, unchanged until the finish)
+    uint32_t rec_pieces = 0;     // ... and their size in 16-B pieces (the checked header's record_bytes)
 };
 
 // One loaded puzzle table: the device tables, the host arrays later calls read, and the facts the
@@ -2307,8 +2312,8 @@ int sparc_sync(void* ctx) {
         if (e & kErrJoin) return fail(c, SPARC_E_STATE, "rule rollout: an audit wave pair did not join (outputs unreliable)");
         if (e & kErrSnapshot)
             return fail(c, SPARC_E_INVALID,
-                        "snapshot / restore / fork / expand: index or record out of range (those envs unchanged, "
-                        "the children of those parents zeroed)");
+                        "snapshot / restore / fork / expand / records audit: index or record out of range (those "
+                        "envs unchanged, the children of those parents zeroed, the bits of those records 0)");
         return fail(c, SPARC_E_INVALID, "device-side puzzle index out of range in a reset");
     }
     return SPARC_OK;
@@ -2753,6 +2758,21 @@ int launch_rules(Ctx* c, const AuditCall& a) {
     }
     const Params p = make_params(c);
     const RulesTab rt = rules_tab(c, c->rl, true);
+    if (a.kind == 3) {
+        // the table-only audit when every puzzle has a region-code table (the rule load's
+        // predicate, as r1r_rollout) and only bits are asked for; else the generic one
+        const uint4* rec = static_cast<const uint4*>(a.rec);
+        const uint32_t M = (uint32_t)a.extent;
+        const dim3 gr((unsigned)((a.extent + kSnapBlock - 1) / kSnapBlock));
+        auto go = [&](auto kern) {
+            kern<<<gr, kSnapBlock, 0, c->stream>>>(p, rt, rec, a.rec_pieces, M, a.bits, a.region, a.fit);
+        };
+        if (c->W == 1 && c->rl.tab_all && !a.region && !a.fit) go(k_rules_rec<1, true>);
+        else if (c->W == 1) go(k_rules_rec<1, false>);
+        else if (c->W == 2) go(k_rules_rec<2, false>);
+        else go(k_rules_rec<4, false>);
+        return launch_check(c);
+    }
     const dim3 g = grid_for(c->n);
     if (c->W == 1) k_rules<1><<<g, kBlock, 0, c->stream>>>(p, rt, a.bits, a.region, a.fit, c->r_memo.get());
     else if (c->W == 2) k_rules<2><<<g, kBlock, 0, c->stream>>>(p, rt, a.bits, a.region, a.fit, c->r_memo.get());
@@ -3557,6 +3577,63 @@ int sparc_expand_host(void* ctx, const sparc_snapshot_info* info, const void* re
     if (reward) HIPCHK(c, hipMemcpyAsync(reward, o, 4 * m, hipMemcpyDeviceToHost, c->stream));
     if (flags) HIPCHK(c, hipMemcpyAsync(flags, o + 4 * m, 4 * m, hipMemcpyDeviceToHost, c->stream));
     if (parent_flags) HIPCHK(c, hipMemcpyAsync(parent_flags, o + 8 * m, m, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
+}
+
+// ---- rule audit of records (sparc_rules_rec.hpp): reads the context's tables only
+int sparc_rules_records_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M,
+                               uint16_t* d_bits, uint8_t* d_region, uint64_t* d_fit) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if (!c->rules) return fail(c, SPARC_E_STATE, "sparc_load_rules has not been called");
+    if ((rc = check_snapshot_info(c, info))) return rc;
+    if (!d_records) return fail(c, SPARC_E_INVALID, "null records");
+    if (reinterpret_cast<uintptr_t>(d_records) & 15u) return fail(c, SPARC_E_INVALID, "records must be 16-B aligned");
+    if (!d_bits) return fail(c, SPARC_E_INVALID, "null bits");
+    if ((rc = check_record_count(c, M, false))) return rc;
+    // a fresh queue for this call, and the call recorded for sparc_rules_finish (sparc_rules_device)
+    HIPCHK(c, hipMemsetAsync(c->fq_count.get(), 0, sizeof(unsigned long long), c->stream));
+    AuditCall a;
+    a.kind = 3;
+    a.extent = (uint64_t)M;
+    a.bits = d_bits;
+    a.region = d_region;
+    a.fit = d_fit;
+    a.rec = d_records;
+    a.rec_pieces = (uint32_t)info->record_bytes / 16u;
+    c->last_audit = a;
+    return launch_rules(c, a);
+}
+
+int sparc_rules_records_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M,
+                             uint16_t* bits, uint8_t* region, uint64_t* fit) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if (!c->rules) return fail(c, SPARC_E_STATE, "sparc_load_rules has not been called");
+    if ((rc = check_snapshot_info(c, info))) return rc;
+    if (!records) return fail(c, SPARC_E_INVALID, "null records");
+    if (!bits) return fail(c, SPARC_E_INVALID, "null bits");
+    if ((rc = check_record_count(c, M, false))) return rc;
+    const size_t m = (size_t)M, bytes = (size_t)info->record_bytes * m, rb = m * 64 * c->W;
+    HIPCHK(c, c->fk_rec.reserve(bytes));
+    HIPCHK(c, c->s_bits.reserve(m));
+    if (region) HIPCHK(c, c->s_region.reserve(rb));
+    if (fit) HIPCHK(c, c->s_fit.reserve(m));
+    HIPCHK(c, hipMemcpyAsync(c->fk_rec.get(), records, bytes, hipMemcpyHostToDevice, c->stream));
+    rc = sparc_rules_records_device(c, info, c->fk_rec.get(), M, c->s_bits.get(), region ? c->s_region.get() : nullptr,
+                                    fit ? c->s_fit.get() : nullptr);
+    if (rc) return rc;
+    // the region rows are final as the kernel wrote them; bits and fit after the finish
+    if (region) HIPCHK(c, hipMemcpyAsync(region, c->s_region.get(), rb, hipMemcpyDeviceToHost, c->stream));
+    uint64_t cnt = 0;
+    if ((rc = read_queue_count(c, cnt))) return rc;
+    if ((rc = finish_queue(c, cnt, c->s_bits.get(), fit ? c->s_fit.get() : nullptr))) return rc;
+    HIPCHK(c, hipMemcpyAsync(bits, c->s_bits.get(), 2 * m, hipMemcpyDeviceToHost, c->stream));
+    if (fit) HIPCHK(c, hipMemcpyAsync(fit, c->s_fit.get(), 8 * m, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 

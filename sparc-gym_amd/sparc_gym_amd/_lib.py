@@ -112,6 +112,10 @@ _SIGS = {
     "sparc_load_rules": ([c_void_p, ctypes.POINTER(SparcRulesTable)], c_int32),
     "sparc_rules_device": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_rules_host": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),
+    "sparc_rules_records_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_void_p,
+                                    c_void_p, c_void_p], c_int32),
+    "sparc_rules_records_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_void_p,
+                                  c_void_p, c_void_p], c_int32),
     "sparc_rules_finish": ([c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_set_rule_limits": ([c_void_p, ctypes.c_uint32, c_uint64], c_int32),
     "sparc_set_variant": ([c_void_p, c_int32, c_int32], c_int32),

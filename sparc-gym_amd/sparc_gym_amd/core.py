@@ -78,6 +78,28 @@ class SparcCore:
     def rules_device(self, d_bits, d_region=None, d_fit=None):
         self._check(self.lib.sparc_rules_device(self.ctx, d_bits, d_region, d_fit))
 
+    def rules_records_device(self, info, d_records, M, d_bits, d_region=None, d_fit=None):
+        """sparc_rules_records_device: the rule audit of M records (bits [M], region [M][64*words],
+        fit [M]); reads the context's tables only (asynchronous; then rules_finish)."""
+        self._check(self.lib.sparc_rules_records_device(self.ctx, ctypes.byref(info), d_records, int(M), d_bits,
+                                                        d_region, d_fit))
+
+    def rules_records_host(self, info, records, region=False, fit=False):
+        """Audit host records [M, record_bytes]: dict of bits [M] uint16 (+ region [M][64*words]
+        uint8, fit [M] uint64 when asked), final (synchronous)."""
+        rec = np.ascontiguousarray(records, np.uint8)
+        if rec.ndim != 2 or rec.shape[1] != info.record_bytes or len(rec) < 1:
+            raise ValueError(f"records must be [M, {info.record_bytes}] uint8 with M >= 1")
+        M, W = len(rec), self.table.words
+        out = {"bits": np.empty(M, np.uint16)}
+        if region:
+            out["region"] = np.empty((M, 64 * W), np.uint8)
+        if fit:
+            out["fit"] = np.empty(M, np.uint64)
+        self._check(self.lib.sparc_rules_records_host(self.ctx, ctypes.byref(info), _ptr(rec), M, _ptr(out["bits"]),
+                                                      _ptr(out.get("region")), _ptr(out.get("fit"))))
+        return out
+
     def rules_finish(self, d_bits, d_fit=None):
         """Finish, on the host and without a node cap, the exact-fit searches of the last audit
         call that passed the GPU's cap, and patch its bits (and fit) in place (synchronous)."""

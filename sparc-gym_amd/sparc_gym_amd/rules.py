@@ -17,7 +17,8 @@ RULE_NAMES = ("reached_target", "path_not_crossing", "no_gap_violations", "all_d
               "square_color_separation", "star_pairing_exact", "triangles_edge_count", "poly_ylop_area",
               "all_rules_satisfied")
 SKIP_LAYERS = ("visited", "gaps", "agent_location", "target_location")
-RULE_SEARCH_EXHAUSTED = 1 << 9   # SPARC_RULE_SEARCH_EXHAUSTED: an exact fit still pending on the host
+RULE_ALL = 1 << 8                # SPARC_RULE_ALL: all_rules_satisfied
+RULE_SEARCH_EXHAUSTED = 1 << 9  # SPARC_RULE_SEARCH_EXHAUSTED: an exact fit still pending on the host
 
 
 def region_map_of(region_bits, x_size, y_size, pitch):

@@ -2,7 +2,7 @@
 (one record per node, any number of them), and one level of a search is one ``expand`` launch
 plus a compaction of the children worth keeping.
 
-The rule both helpers follow is the reference's own: a state that is done (terminated or
+The rule the helpers follow is the reference's own: a state that is done (terminated or
 truncated, step(), SPaRC_Gym.py:1192-1199) has no successors, and the successors of a live state
 are its legal actions (_get_legal_actions, 1024-1051).  Illegal actions, which ``expand`` also
 steps (the no-move state with step + 1), are dropped here.
@@ -17,7 +17,10 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .rules import RULE_ALL
+
 DONE_BITS = 3   # flags bit 0 terminated, bit 1 truncated
+TERMINATED = 1  # flags bit 0: the agent is on the target (step(), SPaRC_Gym.py:1192)
 
 
 def _done_mask(done, M, device):
@@ -119,3 +122,94 @@ def enumerate_paths(vec, puzzle_indices, max_depth=None, max_frontier=1 << 22):
         solution[r] = acts[::-1]
     return {"nodes": np.stack(nodes, 1), "solved": np.stack(solved, 1), "ended": np.stack(ended, 1),
             "solution": solution}
+
+
+def solve_by_rules(vec, puzzle_indices, max_frontier=1 << 22):
+    """Every self-avoiding path from the start to the target of each of ``puzzle_indices`` (one
+    root per entry: that puzzle's reset state, all roots at once), with the puzzle's own verdict on
+    it: the rule audit of the state the path ends in (``vec.audit_records``), beside the verdict of
+    the stored solution list (the last step's reward code).
+
+    The tree of forward moves is walked breadth-first with ``expand_frontier``.  On a traceback
+    env the legal moves include the pop back to the previous point; those children (one point
+    shorter than their parent, ``Snapshot.fields()['path_len']``) are dropped, so the tree is the
+    same with and without traceback.  A node whose step terminated has reached the target
+    (SPaRC_Gym.py:1192): these are the only states for which ``all_rules_satisfied`` can hold
+    (931-950), and the only ones audited.  A path has fewer moves than the lattice has points, so
+    ``vec.max_steps`` must be at least that (ValueError otherwise: a truncation would cut paths
+    short silently).  RuntimeError if a level holds more than ``max_frontier`` nodes.
+
+    The roots come from ``vec.reset`` and ``vec.snapshot``, so ``vec`` needs at least
+    ``len(puzzle_indices)`` envs and its state is overwritten.
+
+    Returns a dict of per-root lists (index r: ``puzzle_indices[r]``), paths in ascending (depth,
+    frontier row) order: ``paths`` the action sequences that reach the target, ``bits`` [K_r] int64
+    their rule bits, ``satisfied`` [K_r] bool (``bits & RULE_ALL``), ``listed`` [K_r] bool (the last
+    step's reward code was +100: the path is in the puzzle's solution list); and ``nodes`` int64
+    [R, D + 1], the forward-move nodes at each depth (column 0: the roots).  Nothing asserts that
+    ``satisfied`` and ``listed`` agree: that is a fact about a dataset."""
+    q = np.asarray(puzzle_indices, np.int64)
+    R = len(q)
+    if q.ndim != 1 or R < 1 or R > vec.num_envs:
+        raise ValueError(f"puzzle_indices must hold 1..{vec.num_envs} puzzle indices")
+    points = max(int(vec.puzzles[int(k)]["x_size"]) * int(vec.puzzles[int(k)]["y_size"]) for k in q)
+    if vec.max_steps < points:
+        raise ValueError(f"max_steps = {vec.max_steps} is below the lattice's {points} points: paths would be "
+                         "truncated")
+    full = np.full(vec.num_envs, q[0], np.int64)
+    full[:R] = q
+    vec.reset(options={"puzzle_index": full})
+    frontier = vec.snapshot(envs=np.arange(R))
+    dev = frontier.records.device
+    root = torch.arange(R, device=dev)
+    nodes = [np.ones(R, np.int64)]
+    levels = []                                          # per level: parent, action, live rows
+    hits = []                                            # per level: (rows, roots, bits, listed) of its target nodes
+    while len(frontier):
+        out = expand_frontier(vec, frontier)             # the frontier holds live nodes only
+        children, parent, action = out["children"], out["parent"], out["action"]
+        code, flags = out["reward_code"], out["flags"]
+        if vec.traceback and len(children):              # drop the pops: one point shorter than the parent
+            fwd = children.fields()["path_len"] > frontier.fields()["path_len"][parent]
+            keep = fwd.nonzero().squeeze(1)
+            children, parent, action = children.select(keep), parent[keep], action[keep]
+            code, flags = code[keep], flags[keep]
+        K = len(children)
+        if K == 0:
+            break
+        if K > max_frontier:
+            raise RuntimeError(f"depth {len(nodes)} holds {K} nodes, more than max_frontier = {max_frontier}")
+        croot = root[parent]
+        nodes.append(torch.bincount(croot, minlength=R).cpu().numpy().astype(np.int64))
+        rows = ((flags & TERMINATED) != 0).nonzero().squeeze(1)
+        if len(rows):
+            bits = vec.audit_records(children.select(rows))["bits"].to(torch.int64) & 0xFFFF
+            hits.append((rows.cpu().numpy(), croot[rows].cpu().numpy(), bits.cpu().numpy(),
+                         (code[rows] == 100).cpu().numpy()))
+        else:
+            hits.append(None)
+        live = ((flags & DONE_BITS) == 0).nonzero().squeeze(1)
+        levels.append((parent.cpu().numpy(), action.cpu().numpy(), live.cpu().numpy()))
+        frontier = children.select(live)
+        root = croot[live]
+    paths = [[] for _ in range(R)]
+    bits_r, listed_r = [[] for _ in range(R)], [[] for _ in range(R)]
+    for d, h in enumerate(hits, start=1):
+        if h is None:
+            continue
+        rows, roots, bits, listed = h
+        acts = np.empty((len(rows), d), np.int64)        # walk all of the level's target nodes back at once
+        row = rows.copy()
+        for lv in range(d, 0, -1):
+            par, act, _ = levels[lv - 1]
+            acts[:, lv - 1] = act[row]
+            prow = par[row]                              # rows of the frontier expanded at level lv
+            row = prow if lv == 1 else levels[lv - 2][2][prow]
+        for k in range(len(rows)):
+            r = int(roots[k])
+            paths[r].append([int(a) for a in acts[k]])
+            bits_r[r].append(int(bits[k]))
+            listed_r[r].append(bool(listed[k]))
+    bits_r = [np.asarray(b, np.int64) for b in bits_r]
+    return {"paths": paths, "bits": bits_r, "satisfied": [(b & RULE_ALL) != 0 for b in bits_r],
+            "listed": [np.asarray(v, np.bool_) for v in listed_r], "nodes": np.stack(nodes, 1)}

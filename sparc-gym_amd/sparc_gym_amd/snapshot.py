@@ -92,6 +92,25 @@ class Snapshot:
             r = torch.from_numpy(np.ascontiguousarray(r, np.uint8))
         return Snapshot(r.to(device), self.info)
 
+    def fields(self):
+        """The scalar fields of every record, decoded by the documented layout (bytes 0-15: pos =
+        x | y<<8 | path length<<16 | off-path depth<<24, aux, current_step, puzzle index): a dict
+        of ``x``, ``y``, ``path_len``, ``step``, ``puzzle_index``, each [M] int64, as numpy arrays
+        for host records and tensors on the records' device otherwise.  Read-only: new arrays,
+        the records are not changed.  ``path_len`` is the number of points on the path (1 after a
+        reset): a traceback pop gives a child one shorter than its parent, a forward move one
+        longer."""
+        r = self.records
+        if isinstance(r, np.ndarray):
+            w = np.ascontiguousarray(r[:, :16], np.uint8).view("<u4").astype(np.int64)   # [M, 4]
+        else:
+            import torch
+            b = r[:, :16].to(torch.int64).reshape(len(r), 4, 4)   # little-endian bytes of the 4 words
+            w = b[:, :, 0] | (b[:, :, 1] << 8) | (b[:, :, 2] << 16) | (b[:, :, 3] << 24)
+        pos = w[:, 0]
+        return {"x": pos & 0xFF, "y": (pos >> 8) & 0xFF, "path_len": (pos >> 16) & 0xFF, "step": w[:, 2],
+                "puzzle_index": w[:, 3]}
+
     # ------------------------------------------------------------------ frontiers
     def select(self, idx):
         """A new ``Snapshot`` of rows ``idx``: a tensor, array or list of integers (any order,

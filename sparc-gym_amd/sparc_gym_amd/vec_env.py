@@ -535,6 +535,40 @@ class SPaRCVecEnv:
         return {"children": Snapshot(children, snap.info), "reward_code": code, "flags": flags,
                 "legal_mask": (pflags >> 2) & 0xF}
 
+    def audit_records(self, snap, region=False, fit=False):
+        """The rule audit of every record of ``snap`` (on the host or the GPU, any number of
+        them), in one launch and without changing or reading any env (k_rules_rec): what
+        ``rule_audit`` gives envs restored from the records.  Returns a dict of GPU tensors:
+        ``bits`` [M] int16, optionally ``region`` [M, 64*words] uint8 and ``fit`` [M] int64, with
+        ``rule_audit``'s meanings.  Loads the rules on first use; needs no reset.  Exact fits past
+        the GPU's node cap are finished on the host, so the bits are final and the call is
+        synchronous.  A record that fails the kernel's checks gets bits 0, fit 0 and a region row
+        of 255, and the next ``core.sync()`` raises.  ValueError naming the field when the
+        snapshot's header does not match this env, as ``restore``."""
+        from .snapshot import info_mismatch
+        self._stream()
+        self._load_rules()
+        bad = info_mismatch(snap.info, self.core.snapshot_info())
+        if bad is not None:
+            raise ValueError(f"snapshot does not match this env: {bad} differs")
+        M = len(snap)
+        if M < 1 or M >= 2**31:
+            raise ValueError("a snapshot of 1 .. 2^31 - 1 records is needed")
+        rec = snap.records
+        if not isinstance(rec, torch.Tensor):
+            rec = torch.from_numpy(np.ascontiguousarray(rec, np.uint8))
+        rec = rec.to(self.device).contiguous()
+        out = {"bits": torch.empty(M, dtype=torch.int16, device=self.device)}
+        if region:
+            out["region"] = torch.empty((M, 64 * self.table.words), dtype=torch.uint8, device=self.device)
+        if fit:
+            out["fit"] = torch.empty(M, dtype=torch.int64, device=self.device)
+        d_fit = out["fit"].data_ptr() if fit else None
+        self.core.rules_records_device(snap.info, rec.data_ptr(), M, out["bits"].data_ptr(),
+                                       out["region"].data_ptr() if region else None, d_fit)
+        self.core.rules_finish(out["bits"].data_ptr(), d_fit)   # rec lives until here: the re-run reads it
+        return out
+
     def state(self):
         """Host snapshot of the per-env state (x, y, path_len, step, puzzle, outcome, visited bits)."""
         torch.cuda.current_stream(self.device).synchronize()
