@@ -63,6 +63,10 @@ int oracle_rollout_obs(const oracle_pool *pool, int n, oracle_env *envs, int T, 
                        int autoreset, int8_t *rew, uint8_t *flags, int32_t *stats, int32_t *vis,
                        int32_t *agent, int xd, int yd);
 uint32_t oracle_rand_action(uint64_t seed, uint64_t env, uint64_t t);
+/* sparc_rules_oracle.c: the rule audit's pass bits of n envs, bits[i] = oracle_rules_bits(rules_pool,
+ * envs[i].pid, &envs[i]) (rules_pool: its oracle_rules_pool); single-threaded, static work buffers;
+ * nonzero when an env's pid is outside the rules pool */
+int oracle_rules_bits_batch(const void *rules_pool, int n, const oracle_env *envs, int16_t *bits);
 #ifdef __cplusplus
 }
 #endif

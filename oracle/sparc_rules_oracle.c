@@ -298,6 +298,18 @@ int oracle_rules_bits(const oracle_rules_pool *rp, int q, const oracle_env *e) {
     return bits;
 }
 
+/* The audit of n envs in one call: bits[i] = oracle_rules_bits(rp, envs[i].pid, &envs[i]) (-1
+ * stays -1), one env after the other on the caller's thread (the audit's work buffers are static).
+ * For traces over every env and step: oracle_rollout one step at a time, this after each. */
+int oracle_rules_bits_batch(const void *rules_pool, int n, const oracle_env *envs, int16_t *bits) {
+    const oracle_rules_pool *rp = (const oracle_rules_pool *)rules_pool;
+    for (int i = 0; i < n; ++i) {
+        if (envs[i].pid < 0 || envs[i].pid >= rp->n_puzzles) return -1;
+        bits[i] = (int16_t)oracle_rules_bits(rp, envs[i].pid, &envs[i]);
+    }
+    return 0;
+}
+
 /* The c3r CPU baseline: oracle_step + the audit `audits` times per env-step (the reference's
  * step() runs _validate_rules at 1227 and again in _get_info 1011), next-step autoreset onto the
  * next puzzle (the reset step: _load_puzzle 182 and _get_info 1011), counter-hash random actions;

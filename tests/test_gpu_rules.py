@@ -213,18 +213,18 @@ def test_rollout_rules_c3r_full_size(on_gpu):
     """The bench's c3r workload at the bench's launch shape (bench.py --config c3r): 65,536 envs of
     the c3 pool, traceback, next-step autoreset, uint8 actions in HBM, the audit after every step,
     TWO back-to-back 2,000-step launches through the bench's own C-ABI call
-    (sparc_rollout_rules_device: k_rollout1r on this pool, 200 tiles of its rings per launch) with
-    the state carried through HBM.  Reward codes, flags and stats equal the plain rollout's (the
-    split kernel, itself oracle-pinned); the rule bits of 256 sampled envs at 200 steps spread over
-    both launches (every step of the first and last tiles, the tile-ring wrap points RT - 1 / RT /
-    2 RT - 1 of a sample of tiles, the steps either side of the launch boundary, and random steps)
-    equal the oracle's audit (oracle/rules_ref.py) of the C oracle's state after that step
-    (SPaRC_Gym.py:941-950, 1227)."""
-    from oracle import COracle
+    (sparc_rollout_rules_device: k_rollout1r on this pool in its default shape, 15-step tiles: 133
+    full tiles and a 5-step one per launch) with the state carried through HBM.  Reward codes,
+    flags and stats equal the plain rollout's (the split kernel, itself oracle-pinned); the rule
+    bits of a fixed random 1,024 env columns at ALL 4,000 steps (every tile boundary and the launch
+    boundary of those envs, about 4 M audits) equal the C oracle's audit after that step
+    (COracle.rollout_rules; SPaRC_Gym.py:941-950, 1227), and at a few hundred of those (env, step)
+    pairs the Python port's too (oracle/rules_ref.py on the oracle's own path)."""
+    from oracle import COracle, RulesCOracle
     from sparc_gym_amd import SPaRCVecEnv, synthetic
     from sparc_gym_amd.puzzles import process_puzzles
     proc = process_puzzles(synthetic.make_puzzles(1024, seed=0, sizes=((3, 3),), full_properties=True))
-    n, T, L, RT = 65536, 2000, 2, 10
+    n, T, L = 65536, 2000, 2
     pids = (np.arange(n, dtype=np.uint64) * 2654435761 % 1024).astype(np.int64)
     kw = dict(processed=proc, traceback=True, autoreset="next_step", observation="compact", rules=True,
               max_steps=2000)
@@ -252,31 +252,32 @@ def test_rollout_rules_c3r_full_size(on_gpu):
     bits = bits.reshape(L * T, n).cpu().numpy().astype(np.uint16)
     assert not (bits & (1 << 9)).any()
     rng = np.random.default_rng(2)
-    idx = np.sort(rng.choice(n, 256, replace=False))
-    steps = set(range(RT)) | set(range(L * T - RT, L * T)) | {T - 2, T - 1, T, T + 1, T + RT - 1, T + RT}
-    for tile in rng.choice(L * T // RT, 40, replace=False):
-        steps |= {int(tile) * RT + RT - 1, int(tile) * RT + RT} - {L * T}
-    steps |= set(int(x) for x in rng.choice(L * T, 120, replace=False))
-    steps = sorted(steps)
-    assert len(steps) >= 200 and min(steps) == 0 and max(steps) == L * T - 1
+    idx = np.sort(rng.choice(n, 1024, replace=False))
+    # the Python port's cross-check: after 16 to 20 steps spread over both launches (the first, the
+    # last, either side of the launch boundary, 16 random ones), 20 of the columns each
+    stops = sorted({0, T - 1, T, L * T - 1} | set(int(x) for x in rng.choice(L * T, 16, replace=False)))
     pool = [{"x_size": p["x_size"], "y_size": p["y_size"], "start": list(p["start_location"]),
              "target": list(p["target_location"]), "solution_count": p["solution_count"],
              "solution_paths": p["solution_paths"], "gaps": p["obs_array"]["gaps"]} for p in proc]
     refp = [dict(p) for p in proc]
+    rules = RulesCOracle(refp)
     o = COracle(pool, len(idx), True, 2000, autoreset=1)
     o.reset(pids[idx])
     an = acts.reshape(L * T, n)[:, torch.from_numpy(idx).cuda()].cpu().numpy()
-    done = 0
-    for t in steps:
-        o.rollout(t + 1 - done, np.ascontiguousarray(an[done:t + 1]))
+    got = bits[:, idx]
+    done = pairs = 0
+    for t in stops:
+        _, _, want = o.rollout_rules(t + 1 - done, rules, an[done:t + 1], t0=done)
+        bad = np.argwhere(got[done:t + 1] != want.astype(np.uint16))
+        assert not len(bad), (len(bad), done + int(bad[0][0]), int(idx[bad[0][1]]))   # count, first (step, env)
         done = t + 1
-        st = o.state()
-        for j, i in enumerate(idx):
-            p = refp[int(st["pid"][j])]
-            vis = st["visited"][j]
-            path = [[x, y] for x in range(p["x_size"]) for y in range(p["y_size"]) if vis[x, y]]
-            want = rules_ref.rule_bits(rules_ref.audit(p, path, (int(st["x"][j]), int(st["y"][j]))))
-            assert int(bits[t, i]) == want, (t, i)
+        for j in rng.choice(len(idx), 20, replace=False):
+            e = o.envs[j]
+            path = [[e.path[k][0], e.path[k][1]] for k in range(e.path_len)]
+            ref = rules_ref.rule_bits(rules_ref.audit(refp[e.pid], path, (e.x, e.y)))
+            assert int(got[t, j]) == ref, (t, int(idx[j]))
+            pairs += 1
+    assert done == L * T and pairs >= 300
     assert len(np.unique(bits)) > 4
 
 
