@@ -113,6 +113,27 @@ static inline uint32_t sparc_rand_action(uint64_t seed, uint64_t env, uint64_t t
     return (uint32_t)(z >> 62);
 }
 
+/* counter-based uniform draw among the set bits of mask & 15 (a legal-action mask,
+ * _get_legal_actions, SPaRC_Gym.py:1024-1051): with z the splitmix64 finaliser of (seed, id, t) as
+ * in sparc_rand_action, n = popcount(mask & 15) and r = ((z >> 32) * n) >> 32, the index of the
+ * r-th set bit counted from bit 0; 0 when no bit is set.  The policy of sparc_playout_device. */
+static inline uint32_t sparc_rand_pick(uint64_t seed, uint64_t id, uint64_t t, uint32_t mask) {
+    uint64_t z = seed + id * 0x9E3779B97F4A7C15ull + t * 0xD1B54A32D192ED03ull;
+    uint32_t m = mask & 15u, n = 0, r, d, seen = 0;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    for (d = 0; d < 4; ++d) n += (m >> d) & 1u;
+    r = (uint32_t)(((z >> 32) * n) >> 32);
+    for (d = 0; d < 4; ++d) {
+        if ((m >> d) & 1u) {
+            if (seen == r) return d;
+            ++seen;
+        }
+    }
+    return 0;
+}
+
 int sparc_abi_version(void);
 const char *sparc_last_error(const void *ctx);
 
@@ -351,6 +372,72 @@ int sparc_expand_device(void *ctx, const sparc_snapshot_info *info, const void *
  * (no alignment requirement) */
 int sparc_expand_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
                       void *children, int8_t *reward, uint8_t *flags, uint8_t *parent_flags);
+
+/* ---- legal-move playouts of records: the value estimate of a Monte-Carlo search ------------------
+ * K independent playouts from each of M records (M >= 1, K >= 1, M * K < 2^31, 1 <= L <= 65535,
+ * K * L < 2^31), under a uniform policy over the LEGAL actions (_get_legal_actions,
+ * SPaRC_Gym.py:1024-1051), in one launch and without touching an env: as with sparc_expand_device
+ * the context supplies its puzzle table, words, pitch, traceback and max_steps only, its env state
+ * is neither read nor written, and sparc_load_puzzles is enough.  A playout never crosses an
+ * episode boundary, so the context's autoreset mode plays no part.
+ * Playout g = j * K + k (k < K) starts from record j and draws with id = id0 + g.  Its end reason:
+ *   SPARC_PLAYOUT_END_INVALID    0  record j fails the checks of sparc_restore_device: every output
+ *                                   of the playout is 0 (first and trace 0xFF, the final record
+ *                                   zeroed), sparc_sync reports the error, others are unaffected
+ *   SPARC_PLAYOUT_END_PENDING    5  the record's last step ended its episode: no step
+ * otherwise, for t = 0 .. L-1: mask = the legal actions of the current state; with
+ * SPARC_PLAYOUT_FORWARD on a traceback context the traceback pop (the move back to path[-2],
+ * 1141-1166) is cleared from it, and
+ *   SPARC_PLAYOUT_END_DEAD_END   4  the cleared mask is empty while the legal one is not: no step
+ * else a = sparc_rand_pick(seed, id, t, mask) (no legal action: a = 0, an illegal step, which
+ * truncates, 1195), one step(a) (1111-1238) as sparc_step_device takes it, and
+ *   SPARC_PLAYOUT_END_TERMINATED 1  the step terminated
+ *   SPARC_PLAYOUT_END_TRUNCATED  2  the step truncated
+ *   SPARC_PLAYOUT_END_HORIZON    3  L steps were taken and none ended the episode.
+ * SPARC_PLAYOUT_FORWARD on a context without traceback has no effect (there is no pop); any other
+ * flag bit is SPARC_E_INVALID.  Outputs (MK = M * K; each may be NULL, at least one must not be):
+ *  code, flags [MK] int8 / uint8: the last step's reward code and flag byte as sparc_step_device
+ *              writes them; 0 if no step was taken
+ *  steps       [MK] uint16: steps taken
+ *  first       [MK] uint8: the first action; 0xFF if no step was taken
+ *  end         [MK] uint8: the end reason
+ *  ret         [MK] int32: the sum of the reward codes of all steps of the playout
+ *  trace       [L][MK] uint8: the action of step t; 0xFF at and after the end
+ *  final_rec   [MK] records (16-B aligned): the state the playout ended in, byte for byte the
+ *              record that sparc_restore_device of record j, the playout's steps through
+ *              sparc_step_device and sparc_snapshot_device give (no step: the restored record)
+ *  stats       [M][4][4] int32, ACCUMULATED (the caller zeroes it): for first action a, {playouts,
+ *              those whose last code was +100, those whose last code was -100, steps}; playouts
+ *              without a step count nowhere.  Integer adds: independent of the order.
+ * info must match the context as for a restore; d_records non-NULL and 16-B aligned.  Device
+ * pointers, asynchronous on the context's stream. */
+#define SPARC_PLAYOUT_FORWARD 1u
+#define SPARC_PLAYOUT_END_INVALID 0
+#define SPARC_PLAYOUT_END_TERMINATED 1
+#define SPARC_PLAYOUT_END_TRUNCATED 2
+#define SPARC_PLAYOUT_END_HORIZON 3
+#define SPARC_PLAYOUT_END_DEAD_END 4
+#define SPARC_PLAYOUT_END_PENDING 5
+typedef struct {
+    int8_t *code;
+    uint8_t *flags;
+    uint16_t *steps;
+    uint8_t *first;
+    uint8_t *end;
+    int32_t *ret;
+    uint8_t *trace;
+    void *final_rec;
+    int32_t *stats;
+} sparc_playout_out;
+int sparc_playout_device(void *ctx, const sparc_snapshot_info *info, const void *d_records, int64_t M,
+                         int32_t K, int32_t L, uint64_t seed, uint64_t id0, uint32_t flags,
+                         const sparc_playout_out *out);
+/* the host-pointer form (records and every member of out on the host, no alignment requirement):
+ * staged through the context's stream, returns after the data have moved; stats is read, added to
+ * and written back */
+int sparc_playout_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
+                       int32_t K, int32_t L, uint64_t seed, uint64_t id0, uint32_t flags,
+                       const sparc_playout_out *out);
 
 /* ---- rule audit: info['rule_status'] (_validate_rules, SPaRC_Gym.py:941-950) ----------------
  * Rule table, packed by sparc_gym_amd/puzzles.py:pack_rules from the processed puzzles, on the

@@ -144,6 +144,26 @@ __device__ __forceinline__ uint32_t uint_rand_action(uint64_t seed, uint64_t env
     return (uint32_t)(z >> 62);
 }
 
+// sparc_rand_pick (sparc_gym_amd.h): the r-th set bit of mask & 15, r uniform in [0, popcount).
+// The bit is selected with compares and masks, never by indexing (see bb_word).
+__device__ __forceinline__ uint32_t uint_rand_pick(uint64_t seed, uint64_t id, uint64_t t, uint32_t mask) {
+    uint64_t z = seed + id * 0x9E3779B97F4A7C15ull + t * 0xD1B54A32D192ED03ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    const uint32_t m = mask & 15u;
+    const uint32_t n = (uint32_t)__builtin_popcount(m);
+    const uint32_t r = (uint32_t)(((z >> 32) * n) >> 32);
+    uint32_t a = 0, seen = 0;
+#pragma unroll
+    for (uint32_t d = 0; d < 4; ++d) {
+        const uint32_t bit = (m >> d) & 1u;
+        a |= (bit & (uint32_t)(seen == r)) ? d : 0u;
+        seen += bit;
+    }
+    return a;
+}
+
 struct RegStack;
 
 template <int W, bool TB, class Stack = RegStack>

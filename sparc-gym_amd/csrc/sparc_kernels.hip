@@ -10,6 +10,7 @@
 //   k_rules    rule audit of the current state                      (_validate_rules, 941-950)
 //   k_snapshot / k_restore  the state as per-env records and back  (sparc_snapshot.hpp)
 //   k_rules_rec  rule audit of state records, without an env      (sparc_rules_rec.hpp)
+//   k_playout  K legal-move playouts of each state record, without an env (sparc_playout.hpp)
 // No MFMA: this is integer / bitboard work, bound by latency and HBM.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -32,6 +33,7 @@
 #include "sparc_rules.hpp"
 #include "sparc_snapshot.hpp"
 #include "sparc_expand.hpp"
+#include "sparc_playout.hpp"
 #include "sparc_rules_rec.hpp"
 #include "sparc_devbuf.hpp"
 #include "sparc_tables.hpp"
@@ -2036,6 +2038,9 @@ struct Ctx {
     DevBuf<uint32_t> fk_idx;
     // sparc_expand_host (sparc_expand.hpp): the children, and reward [4M] | flags [4M] | parent flags [M]
     DevBuf<uint8_t> ex_child, ex_out;
+    // sparc_playout_host (sparc_playout.hpp): the per-playout outputs and the trace, the stats
+    DevBuf<uint8_t> po_out;
+    DevBuf<int32_t> po_stats;
     DevBuf<uint16_t> s_bits;        // per-env audit outputs of the host-pointer / one-env calls
     DevBuf<uint8_t> s_region;
     DevBuf<uint64_t> s_fit;
@@ -2312,7 +2317,7 @@ int sparc_sync(void* ctx) {
         if (e & kErrJoin) return fail(c, SPARC_E_STATE, "rule rollout: an audit wave pair did not join (outputs unreliable)");
         if (e & kErrSnapshot)
             return fail(c, SPARC_E_INVALID,
-                        "snapshot / restore / fork / expand / records audit: index or record out of range (those "
+                        "snapshot / restore / fork / expand / playout / records audit: index or record out of range (those "
                         "envs unchanged, the children of those parents zeroed, the bits of those records 0)");
         return fail(c, SPARC_E_INVALID, "device-side puzzle index out of range in a reset");
     }
@@ -3577,6 +3582,96 @@ int sparc_expand_host(void* ctx, const sparc_snapshot_info* info, const void* re
     if (reward) HIPCHK(c, hipMemcpyAsync(reward, o, 4 * m, hipMemcpyDeviceToHost, c->stream));
     if (flags) HIPCHK(c, hipMemcpyAsync(flags, o + 4 * m, 4 * m, hipMemcpyDeviceToHost, c->stream));
     if (parent_flags) HIPCHK(c, hipMemcpyAsync(parent_flags, o + 8 * m, m, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
+}
+
+// ---- legal-move playouts of records (sparc_playout.hpp): reads the context's tables only
+static int check_playout_args(Ctx* c, const sparc_snapshot_info* info, const void* records, int64_t M, int32_t K,
+                              int32_t L, uint32_t flags, const sparc_playout_out* out, bool device) {
+    int rc = check_snapshot_info(c, info);
+    if (rc) return rc;
+    if (!records) return fail(c, SPARC_E_INVALID, "null records");
+    if (!out) return fail(c, SPARC_E_INVALID, "null out");
+    if (M < 1) return fail(c, SPARC_E_INVALID, "M must be at least 1");
+    if (K < 1) return fail(c, SPARC_E_INVALID, "K must be at least 1");
+    if (M > 0x7FFFFFFFll || (uint64_t)M * (uint64_t)K > 0x7FFFFFFFull)
+        return fail(c, SPARC_E_INVALID, "M * K must be below 2^31");
+    if (L < 1 || L > 65535) return fail(c, SPARC_E_INVALID, "L must be in 1..65535");
+    if ((uint64_t)K * (uint64_t)L > 0x7FFFFFFFull) return fail(c, SPARC_E_INVALID, "K * L must be below 2^31");
+    if (flags & ~SPARC_PLAYOUT_FORWARD) return fail(c, SPARC_E_INVALID, "unknown bits in flags");
+    if (!out->code && !out->flags && !out->steps && !out->first && !out->end && !out->ret && !out->trace &&
+        !out->final_rec && !out->stats)
+        return fail(c, SPARC_E_INVALID, "out: at least one output is needed");
+    if (device) {
+        if ((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(out->final_rec)) & 15u)
+            return fail(c, SPARC_E_INVALID, "records and out->final_rec must be 16-B aligned");
+        if ((reinterpret_cast<uintptr_t>(out->steps) & 1u) ||
+            ((reinterpret_cast<uintptr_t>(out->ret) | reinterpret_cast<uintptr_t>(out->stats)) & 3u))
+            return fail(c, SPARC_E_INVALID, "out->steps, out->ret and out->stats must be aligned to their type");
+    }
+    return SPARC_OK;
+}
+
+int sparc_playout_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M, int32_t K,
+                         int32_t L, uint64_t seed, uint64_t id0, uint32_t flags, const sparc_playout_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_playout_args(c, info, d_records, M, K, L, flags, out, true))) return rc;
+    const Params p = make_params(c);
+    const uint32_t MK = (uint32_t)M * (uint32_t)K;
+    const PlayoutOut o{out->code, out->flags, out->steps,  out->first, out->end,
+                       out->ret,  out->trace, static_cast<uint4*>(out->final_rec), out->stats};
+    dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
+        k_playout<decltype(w)::value, decltype(tb)::value><<<grid_for(MK), kSnapBlock, 0, c->stream>>>(
+            p, static_cast<const uint4*>(d_records), MK, (uint32_t)K, (uint32_t)L, seed, id0, flags, o);
+    });
+    return launch_check(c);
+}
+
+int sparc_playout_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M, int32_t K,
+                       int32_t L, uint64_t seed, uint64_t id0, uint32_t flags, const sparc_playout_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_playout_args(c, info, records, M, K, L, flags, out, false))) return rc;
+    const size_t m = (size_t)M, mk = m * (size_t)K, bytes = (size_t)info->record_bytes * m;
+    // one scratch: ret [mk] int32 | steps [mk] uint16 | code, flags, first, end [mk] | trace [L][mk]
+    const size_t o_ret = 0, o_steps = 4 * mk, o_code = 6 * mk, o_flags = 7 * mk, o_first = 8 * mk, o_end = 9 * mk,
+                 o_trace = 10 * mk, total = o_trace + (out->trace ? (size_t)L * mk : 0);
+    HIPCHK(c, c->fk_rec.reserve(bytes));
+    HIPCHK(c, c->po_out.reserve(total));
+    if (out->final_rec) HIPCHK(c, c->ex_child.reserve((size_t)info->record_bytes * mk));
+    if (out->stats) {
+        HIPCHK(c, c->po_stats.reserve(16 * m));
+        HIPCHK(c, hipMemcpyAsync(c->po_stats.get(), out->stats, 64 * m, hipMemcpyHostToDevice, c->stream));
+    }
+    uint8_t* o = c->po_out.get();
+    HIPCHK(c, hipMemcpyAsync(c->fk_rec.get(), records, bytes, hipMemcpyHostToDevice, c->stream));
+    sparc_playout_out d{};
+    d.code = out->code ? reinterpret_cast<int8_t*>(o + o_code) : nullptr;
+    d.flags = out->flags ? o + o_flags : nullptr;
+    d.steps = out->steps ? reinterpret_cast<uint16_t*>(o + o_steps) : nullptr;
+    d.first = out->first ? o + o_first : nullptr;
+    d.end = out->end ? o + o_end : nullptr;
+    d.ret = out->ret ? reinterpret_cast<int32_t*>(o + o_ret) : nullptr;
+    d.trace = out->trace ? o + o_trace : nullptr;
+    d.final_rec = out->final_rec ? c->ex_child.get() : nullptr;
+    d.stats = out->stats ? c->po_stats.get() : nullptr;
+    if ((rc = sparc_playout_device(c, info, c->fk_rec.get(), M, K, L, seed, id0, flags, &d))) return rc;
+    if (out->code) HIPCHK(c, hipMemcpyAsync(out->code, d.code, mk, hipMemcpyDeviceToHost, c->stream));
+    if (out->flags) HIPCHK(c, hipMemcpyAsync(out->flags, d.flags, mk, hipMemcpyDeviceToHost, c->stream));
+    if (out->steps) HIPCHK(c, hipMemcpyAsync(out->steps, d.steps, 2 * mk, hipMemcpyDeviceToHost, c->stream));
+    if (out->first) HIPCHK(c, hipMemcpyAsync(out->first, d.first, mk, hipMemcpyDeviceToHost, c->stream));
+    if (out->end) HIPCHK(c, hipMemcpyAsync(out->end, d.end, mk, hipMemcpyDeviceToHost, c->stream));
+    if (out->ret) HIPCHK(c, hipMemcpyAsync(out->ret, d.ret, 4 * mk, hipMemcpyDeviceToHost, c->stream));
+    if (out->trace) HIPCHK(c, hipMemcpyAsync(out->trace, d.trace, (size_t)L * mk, hipMemcpyDeviceToHost, c->stream));
+    if (out->final_rec)
+        HIPCHK(c, hipMemcpyAsync(out->final_rec, d.final_rec, (size_t)info->record_bytes * mk, hipMemcpyDeviceToHost,
+                                 c->stream));
+    if (out->stats) HIPCHK(c, hipMemcpyAsync(out->stats, d.stats, 64 * m, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 

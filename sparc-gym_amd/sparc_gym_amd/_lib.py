@@ -63,6 +63,16 @@ class SparcSnapshotInfo(ctypes.Structure):
 
 assert ctypes.sizeof(SparcSnapshotInfo) == 40
 
+PLAYOUT_FORWARD = 1   # SPARC_PLAYOUT_FORWARD
+# SPARC_PLAYOUT_END_*: why a playout ended
+END_INVALID, END_TERMINATED, END_TRUNCATED, END_HORIZON, END_DEAD_END, END_PENDING = range(6)
+
+
+class SparcPlayoutOut(ctypes.Structure):
+    """sparc_playout_out: the nine outputs of sparc_playout_device / _host, each may be NULL."""
+    _fields_ = [(k, c_void_p) for k in ("code", "flags", "steps", "first", "end", "ret", "trace", "final_rec",
+                                        "stats")]
+
 
 _SIGS = {
     "sparc_abi_version": ([], c_int32),
@@ -109,6 +119,10 @@ _SIGS = {
                              c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_expand_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_void_p,
                            c_void_p, c_void_p, c_void_p], c_int32),
+    "sparc_playout_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_int32, c_int32,
+                              c_uint64, c_uint64, ctypes.c_uint32, ctypes.POINTER(SparcPlayoutOut)], c_int32),
+    "sparc_playout_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_int32, c_int32,
+                            c_uint64, c_uint64, ctypes.c_uint32, ctypes.POINTER(SparcPlayoutOut)], c_int32),
     "sparc_load_rules": ([c_void_p, ctypes.POINTER(SparcRulesTable)], c_int32),
     "sparc_rules_device": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_rules_host": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),

@@ -320,6 +320,49 @@ class SparcCore:
                                                _ptr(flags), _ptr(pflags)))
         return children, rew, flags, pflags
 
+    # ---------------------------------------------------------------- legal-move playouts of records
+    def playout_device(self, info, d_records, M, K, L, seed=0, id0=0, flags=0, d_code=None, d_flags=None,
+                       d_steps=None, d_first=None, d_end=None, d_return=None, d_trace=None, d_final=None,
+                       d_stats=None):
+        """sparc_playout_device: K playouts of at most L steps from each of M records, uniform over
+        the legal actions; outputs [M * K] (trace [L][M * K], stats [M][4][4] accumulated), each
+        may be None; reads the context's tables only (asynchronous)."""
+        out = _lib.SparcPlayoutOut(d_code, d_flags, d_steps, d_first, d_end, d_return, d_trace, d_final, d_stats)
+        self._check(self.lib.sparc_playout_device(self.ctx, ctypes.byref(info), d_records, int(M), int(K), int(L),
+                                                  int(seed) & (2**64 - 1), int(id0) & (2**64 - 1), int(flags),
+                                                  ctypes.byref(out)))
+
+    def playout_host(self, info, records, K, L, seed=0, id0=0, flags=0, trace=False, final=False, stats=None):
+        """Play out host records [M, record_bytes]: a dict of host arrays ``code`` int8, ``flags``
+        uint8, ``steps`` uint16, ``first`` uint8, ``end`` uint8, ``ret`` int32 (each [M, K]),
+        optionally ``trace`` [L, M, K] uint8 and ``final`` [M * K, record_bytes] uint8, and
+        ``stats`` [M, 4, 4] int32: a fresh zeroed array, or the given one added to (synchronous)."""
+        rec = np.ascontiguousarray(records, np.uint8)
+        if rec.ndim != 2 or rec.shape[1] != info.record_bytes or len(rec) < 1:
+            raise ValueError(f"records must be [M, {info.record_bytes}] uint8 with M >= 1")
+        M, K, L = len(rec), int(K), int(L)
+        if K < 1 or M * K >= 2**31 or not 1 <= L <= 65535 or K * L >= 2**31:
+            raise ValueError("K >= 1, M * K < 2^31, 1 <= L <= 65535 and K * L < 2^31 are needed")
+        if stats is None:
+            stats = np.zeros((M, 4, 4), np.int32)
+        elif not (isinstance(stats, np.ndarray) and stats.dtype == np.int32 and stats.shape == (M, 4, 4)
+                  and stats.flags.c_contiguous):
+            raise ValueError(f"stats must be a C-contiguous int32 array [{M}, 4, 4]")
+        out = {"code": np.empty((M, K), np.int8), "flags": np.empty((M, K), np.uint8),
+               "steps": np.empty((M, K), np.uint16), "first": np.empty((M, K), np.uint8),
+               "end": np.empty((M, K), np.uint8), "ret": np.empty((M, K), np.int32), "stats": stats}
+        if trace:
+            out["trace"] = np.empty((L, M, K), np.uint8)
+        if final:
+            out["final"] = np.empty((M * K, rec.shape[1]), np.uint8)
+        o = _lib.SparcPlayoutOut(_ptr(out["code"]), _ptr(out["flags"]), _ptr(out["steps"]), _ptr(out["first"]),
+                                 _ptr(out["end"]), _ptr(out["ret"]), _ptr(out.get("trace")), _ptr(out.get("final")),
+                                 _ptr(stats))
+        self._check(self.lib.sparc_playout_host(self.ctx, ctypes.byref(info), _ptr(rec), M, K, L,
+                                                int(seed) & (2**64 - 1), int(id0) & (2**64 - 1), int(flags),
+                                                ctypes.byref(o)))
+        return out
+
 
 def visited_planes(bits, table: PuzzleTable, x_dim=None, y_dim=None):
     """Decode visited bitboards [words][N] into int32 planes [N][x_dim][y_dim] (host)."""

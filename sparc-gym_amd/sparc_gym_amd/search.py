@@ -124,6 +124,64 @@ def enumerate_paths(vec, puzzle_indices, max_depth=None, max_frontier=1 << 22):
             "solution": solution}
 
 
+def rand_pick(seed, id, t, mask):
+    """``sparc_rand_pick`` (include/sparc_gym_amd.h) on numpy arrays, broadcast together: the
+    uniform draw of ``SPaRCVecEnv.playout`` among the set bits of ``mask & 15``.  With ``z`` the
+    splitmix64 finaliser of ``(seed, id, t)``, ``n = popcount(mask & 15)`` and
+    ``r = ((z >> 32) * n) >> 32``, the index of the r-th set bit counted from bit 0; 0 for an
+    empty mask.  uint64 arithmetic throughout; returns int64."""
+    def u(v):   # a Python int is taken modulo 2^64, as the C argument is
+        return np.uint64(v & (2**64 - 1)) if isinstance(v, int) else np.asarray(v).astype(np.uint64)
+
+    seed, id, t, m = np.broadcast_arrays(u(seed), u(id), u(t), u(mask) & np.uint64(15))
+    with np.errstate(over="ignore"):
+        z = seed + id * np.uint64(0x9E3779B97F4A7C15) + t * np.uint64(0xD1B54A32D192ED03)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    bits = [(m >> np.uint64(d)) & np.uint64(1) for d in range(4)]
+    n = bits[0] + bits[1] + bits[2] + bits[3]
+    r = ((z >> np.uint64(32)) * n) >> np.uint64(32)          # < 2^34: no overflow
+    out = np.zeros(m.shape, np.int64)
+    seen = np.zeros(m.shape, np.uint64)
+    for d in range(4):
+        out = np.where((bits[d] == 1) & (seen == r), d, out)
+        seen = seen + bits[d]
+    return out
+
+
+def monte_carlo(vec, snap, playouts, horizon, seed=0, forward_only=None):
+    """Flat Monte-Carlo evaluation of every record of ``snap`` (M of them): one
+    ``vec.playout(snap, playouts, horizon, ...)`` launch with the trace, reduced per record and
+    first action.  ``forward_only`` defaults to ``vec.traceback`` (a uniform walk that may undo
+    its moves rarely arrives).  Touches no env.
+
+    Returns a dict: ``visits``, ``wins``, ``losses`` [M, 4] int64 (playouts that began with action
+    a; those whose last reward code was +100 / -100) and ``mean_steps`` [M, 4] float64 (0 where
+    no visit), as numpy arrays; ``best_action`` [M] int64: the action with the highest
+    ``wins / visits`` among those visited (only legal actions are ever drawn; ties go to the
+    lowest action), -1 where no playout took a step; ``solution``: per record, the action list
+    of its shortest playout that ended with code +100 (the lowest k wins ties), or None."""
+    if forward_only is None:
+        forward_only = bool(vec.traceback)
+    out = vec.playout(snap, playouts, horizon, seed=seed, forward_only=forward_only, trace=True, stats=True)
+    stats = out["stats"].cpu().numpy().astype(np.int64)      # [M, 4, 4]
+    visits, wins, losses, steps = (stats[:, :, c] for c in range(4))
+    mean_steps = np.where(visits > 0, steps / np.maximum(visits, 1), 0.0)
+    rate = np.where(visits > 0, wins / np.maximum(visits, 1), -1.0)
+    best = np.where((visits > 0).any(1), rate.argmax(1), -1).astype(np.int64)   # argmax: the first maximum
+    code = out["reward_code"].cpu().numpy()
+    nsteps = out["steps"].cpu().numpy().astype(np.int64)
+    trace = out["trace"].cpu().numpy()                       # [L, M, K]
+    won = (code == 100) & (nsteps > 0)
+    solution = [None] * len(visits)
+    for j in np.nonzero(won.any(1))[0]:
+        k = int(np.where(won[j], nsteps[j], np.iinfo(np.int64).max).argmin())   # the first minimum
+        solution[j] = [int(a) for a in trace[:nsteps[j, k], j, k]]
+    return {"visits": visits, "wins": wins, "losses": losses, "mean_steps": mean_steps, "best_action": best,
+            "solution": solution}
+
+
 def solve_by_rules(vec, puzzle_indices, max_frontier=1 << 22):
     """Every self-avoiding path from the start to the target of each of ``puzzle_indices`` (one
     root per entry: that puzzle's reset state, all roots at once), with the puzzle's own verdict on

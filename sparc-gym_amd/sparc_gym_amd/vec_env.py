@@ -32,12 +32,16 @@ of any env on the same puzzle table, ``fork(src)`` makes env ``i`` a copy of env
 position fanned out to every env for playouts, beam search or MCTS, or a run saved and resumed.
 ``expand(snap)`` returns all four successors of any number of records in one launch without
 touching an env (the one-ply step of a tree search; ``sparc_gym_amd.search`` builds on it).
+``playout(snap, K, L)`` plays K random legal-move continuations of every record to the end of
+its episode or L steps, again in one launch without an env, with per-root statistics
+(``search.monte_carlo``).
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from . import _lib
 from .core import SparcCore
 from .env import load_puzzle_source
 from .puzzles import pack_rules, pack_table, process_puzzles
@@ -534,6 +538,65 @@ class SPaRCVecEnv:
                                 pflags.data_ptr())
         return {"children": Snapshot(children, snap.info), "reward_code": code, "flags": flags,
                 "legal_mask": (pflags >> 2) & 0xF}
+
+    def playout(self, snap, playouts, horizon, seed=0, id0=0, forward_only=False, trace=False, final=False,
+                stats=True):
+        """``playouts`` (K) independent random continuations of every record of ``snap`` (M of
+        them), each at most ``horizon`` (L) steps, uniform over the LEGAL actions of each state
+        (``search.rand_pick(seed, id0 + j * K + k, t, mask)``), in one launch and without changing
+        or reading any env (k_playout).  A playout ends with the step that terminates or
+        truncates, never in the next episode, whatever this env's ``autoreset``.
+        ``forward_only``: on a traceback env the pop back to the previous point is never drawn; a
+        state whose only legal move is the pop ends the playout (a dead end).  Without traceback
+        it has no effect.
+
+        Returns a dict of GPU tensors, [M, K] each: ``reward_code`` int8 and ``flags`` uint8 of the
+        last step (0 without one), ``steps`` int32 the steps taken,
+        ``first`` uint8 the first action (255: none), ``end`` uint8 the end reason (``_lib.END_*``:
+        0 bad record, 1 terminated, 2 truncated, 3 horizon, 4 dead end, 5 the record was already
+        done), ``return`` int32 the sum of the reward codes; with ``trace`` the actions [L, M, K]
+        uint8 (255 at and after the end); with ``final`` a ``Snapshot`` of the M * K end states
+        (row ``j * K + k``); with ``stats`` [M, 4, 4] int32, per record and first action
+        {playouts, ended with code +100, ended with code -100, steps}.  A record that fails the
+        kernel's checks gives end 0 and zeroed outputs, and the next ``core.sync()`` raises.
+        ValueError naming the field when the snapshot's header does not match this env."""
+        from .snapshot import Snapshot, info_mismatch
+        self._stream()
+        bad = info_mismatch(snap.info, self.core.snapshot_info())
+        if bad is not None:
+            raise ValueError(f"snapshot does not match this env: {bad} differs")
+        M, K, L = len(snap), int(playouts), int(horizon)
+        if M < 1 or K < 1 or M * K >= 2**31:
+            raise ValueError("at least one record and one playout, fewer than 2^31 playouts in all, are needed")
+        if not 1 <= L <= 65535 or K * L >= 2**31:
+            raise ValueError("horizon must be in 1..65535 with playouts * horizon below 2^31")
+        rec = snap.records
+        if not isinstance(rec, torch.Tensor):
+            rec = torch.from_numpy(np.ascontiguousarray(rec, np.uint8))
+        rec = rec.to(self.device).contiguous()
+        MK = M * K
+        dev = self.device
+        ret = torch.empty((M, K), dtype=torch.int32, device=dev)
+        steps = torch.empty((M, K), dtype=torch.int16, device=dev)
+        b = torch.empty((4, M, K), dtype=torch.uint8, device=dev)     # code | flags | first | end
+        out = {"reward_code": b[0].view(torch.int8), "flags": b[1], "steps": steps, "first": b[2], "end": b[3],
+               "return": ret}
+        if trace:
+            out["trace"] = torch.empty((L, M, K), dtype=torch.uint8, device=dev)
+        fin = torch.empty((MK, snap.info.record_bytes), dtype=torch.uint8, device=dev) if final else None
+        if stats:
+            out["stats"] = torch.zeros((M, 4, 4), dtype=torch.int32, device=dev)
+        self.core.playout_device(snap.info, rec.data_ptr(), M, K, L, seed, id0,
+                                 _lib.PLAYOUT_FORWARD if forward_only else 0, d_code=b[0].data_ptr(),
+                                 d_flags=b[1].data_ptr(), d_steps=steps.data_ptr(), d_first=b[2].data_ptr(),
+                                 d_end=b[3].data_ptr(), d_return=ret.data_ptr(),
+                                 d_trace=out["trace"].data_ptr() if trace else None,
+                                 d_final=fin.data_ptr() if final else None,
+                                 d_stats=out["stats"].data_ptr() if stats else None)
+        out["steps"] = steps.to(torch.int32) & 0xFFFF                 # the kernel writes uint16
+        if final:
+            out["final"] = Snapshot(fin, snap.info)
+        return out
 
     def audit_records(self, snap, region=False, fit=False):
         """The rule audit of every record of ``snap`` (on the host or the GPU, any number of
