@@ -146,7 +146,11 @@ int sparc_set_stream(void *ctx, void *stream);
 int sparc_use_own_stream(void *ctx);
 int sparc_sync(void *ctx);
 
-/* _process_puzzles output -> device (SPaRC_Gym.py:88, 219-368); host arrays, copied. */
+/* _process_puzzles output -> device (SPaRC_Gym.py:88, 219-368); host arrays, copied.
+ * The path length is an 8-bit field of the env state and of a snapshot record (pos bits 16-23),
+ * so a puzzle whose path could hold more than 255 points (its open points, plus the start where
+ * that is closed) is refused with SPARC_E_INVALID: a gap-free 16x16 lattice (256 points) is, the
+ * same lattice with one point closed is not. */
 int sparc_load_puzzles(void *ctx, const sparc_puzzle_table *table);
 
 /* reset / _load_puzzle (SPaRC_Gym.py:1057-1108, 141-187) for every env with mask[i] != 0

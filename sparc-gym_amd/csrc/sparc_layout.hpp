@@ -15,6 +15,9 @@ namespace sparc {
 
 constexpr uint32_t kNone = 0xFFFFu;         // no child in a trie record's 16-bit field
 constexpr size_t kMaxDynLds = 160 * 1024;   // one workgroup may own all 160 KiB (gfx950)
+// points of the longest path: the length is 8 bits of the state's pos word and of a snapshot
+// record (bits 16-23), so the loaders refuse a puzzle whose path could hold more
+constexpr uint32_t kMaxPathPoints = 255;
 
 // W = 1 split kernel (k_rollout1s): the pitches its window arithmetic covers
 SPARC_HD constexpr bool split1_pitch_ok(uint32_t P) { return P >= 3u && P <= 9u; }

@@ -84,6 +84,20 @@ inline BuildError build_puzzle_tables(const sparc_puzzle_table* t, int W, uint32
             snprintf(m, sizeof m, "puzzle %d: start/target outside the lattice", q);
             return invalid(m);
         }
+        // the path length is an 8-bit field of the state (pos bits 16-23, sparc_env.hpp) and of a
+        // snapshot record: a path through every point a path can hold (the open points, and the
+        // start even where it is closed) must stay at or below kMaxPathPoints
+        uint32_t pts = 0;
+        for (uint32_t x = 0; x < X; ++x)
+            for (uint32_t y = 0; y < Y; ++y) {
+                const uint32_t b = x * pitch + y;
+                pts += (uint32_t)(((t->open[(size_t)q * W + (b >> 6)] >> (b & 63)) & 1ull) || (x == sx && y == sy));
+            }
+        if (pts > kMaxPathPoints) {
+            snprintf(m, sizeof m, "puzzle %d: a path could hold %u points, at most %u fit (8-bit path length)", q, pts,
+                     kMaxPathPoints);
+            return invalid(m);
+        }
         if ((fl & 2u) && (cnt == 0 || (uint64_t)base + cnt > (uint64_t)t->num_nodes || cnt > (W == 1 ? 0x7FFFu : 0xFFFFu))) {
             snprintf(m, sizeof m, "puzzle %d: trie range out of bounds", q);
             return invalid(m);

@@ -26,6 +26,7 @@ COLOR_TO_NUMBER = {"red": 1, "blue": 2, "yellow": 3, "green": 4, "black": 5, "pu
                    "orange": 7, "white": 8}   # SPaRC_Gym.py:310
 BASE_KEYS = ("visited", "gaps", "agent_location", "target_location")
 _NONE = 0xFFFF
+MAX_PATH_POINTS = 255   # the path length is an 8-bit field of the env state and of a snapshot record
 _DIRS = ((1, 0), (0, -1), (-1, 0), (0, 1))   # right, up, left, down (SPaRC_Gym.py:212-217)
 _UNBOUND = object()
 # yaml.safe_load (SPaRC_Gym.py:261, 266) through libyaml when PyYAML has it: the same
@@ -187,7 +188,8 @@ def lattice_geometry(puzzles, pitch=None, words=None):
     bits = (x_max - 1) * pitch + y_max
     need = 2 if bits <= 128 else 4 if bits <= 256 else None
     if need is None:
-        raise ValueError(f"lattice {x_max}x{y_max} exceeds the 256-bit bitboard (15x15 lattices max)")
+        raise ValueError(f"lattice {x_max}x{y_max} exceeds the 256-bit bitboard: (x_max - 1) * pitch + y_max must be "
+                         f"at most 256 bits, and a puzzle may have at most {MAX_PATH_POINTS} points a path can visit")
     words = need if words is None else int(words)
     if words not in (2, 4) or words < need:
         raise ValueError(f"words={words} cannot hold a {x_max}x{pitch} lattice")
@@ -265,6 +267,11 @@ def pack_table(puzzles, pitch=None, words=None):
             raise ValueError(f"puzzle {q}: start/target outside the {X}x{Y} lattice")
         gaps = np.asarray(p["obs_array"]["gaps"])
         xs, ys = np.nonzero(gaps[:X, :Y] == 0)
+        # the points a path can hold: the open ones, and the start even where it is a gap
+        points = len(xs) + int(gaps[sx, sy] != 0)
+        if points > MAX_PATH_POINTS:
+            raise ValueError(f"puzzle {q}: a path could hold {points} points, at most {MAX_PATH_POINTS} points fit "
+                             f"(8-bit path length)")
         bits = xs.astype(np.int64) * pitch + ys
         words_arr = np.zeros(words, np.uint64)
         for w in range(words):

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from sparc_gym_amd import synthetic
-from sparc_gym_amd.puzzles import pack_rules, pack_table, process_puzzles
+from sparc_gym_amd.puzzles import lattice_geometry, pack_rules, pack_table, process_puzzles
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "sparc-gym_amd", "csrc")
@@ -179,3 +179,36 @@ def test_every_rejection_keeps_its_code_and_text(tables_main, tmp_path, pool7, p
          edit=lambda t, r: setw(r.inst, 0, (int(r.inst[0]) & 0x7FF) | (len(r.shape_area) << 11)))
     out = tables_main("reject", *[d for d, _ in cases])
     assert out == [f"{INVALID}|{text}" for _, text in cases]
+
+
+def test_a_path_holds_at_most_255_points(tables_main, tmp_path):
+    """The path length is an 8-bit field of the state and of a snapshot record, so both loaders
+    refuse a puzzle whose path could hold 256 points: the gap-free 16x16 lattice, the one shape
+    the 256-bit board holds and the length does not.  One closed point makes it legal."""
+    from long_pools import square_pool
+    with pytest.raises(ValueError, match="255 points"):
+        pack_table(square_pool(16, closed=False))
+    with pytest.raises(ValueError, match="256 bits.*255 points"):      # past the board: the rule, not "15x15 max"
+        lattice_geometry([{"x_size": 17, "y_size": 17}])
+    t255 = pack_table(square_pool(16, closed=True))
+    assert (t255.words, t255.pitch) == (4, 16)
+    assert sum(bin(int(w)).count("1") for w in t255.open[0]) == 255
+    t225 = pack_table(square_pool(15, closed=False))
+    assert (t225.words, t225.pitch) == (4, 15)
+    assert sum(bin(int(w)).count("1") for w in t225.open[0]) == 225
+    t81 = pack_table(square_pool(9, closed=False))
+    assert (t81.words, t81.pitch) == (2, 9)
+    # pitch 16 never reaches the multi-word split kernel; the gap-free 9x9 and 15x15 tables do
+    ok = [write_pool(tmp_path / "p255", t255, expect_split_w=0), write_pool(tmp_path / "p225", t225, expect_split_w=1),
+          write_pool(tmp_path / "p81", t81, expect_split_w=1)]
+    assert tables_main("check", *ok) == [f"ok {d}" for d in ok]
+    # the same table with point (0, 0) of puzzle 2 opened: 256 open points
+    t256 = _copy(t255)
+    t256.open[2, 0] |= np.uint64(1)
+    # and with the start of puzzle 1 moved onto the closed point: 255 open points and the start
+    tstart = _copy(t255)
+    tstart.info[1, 0] = int(tstart.info[1, 0]) & 0x0000FFFF
+    bad = [write_pool(tmp_path / "p256", t256), write_pool(tmp_path / "pstart", tstart)]
+    assert tables_main("reject", *bad) == [
+        f"{INVALID}|puzzle 2: a path could hold 256 points, at most 255 fit (8-bit path length)",
+        f"{INVALID}|puzzle 1: a path could hold 256 points, at most 255 fit (8-bit path length)"]
