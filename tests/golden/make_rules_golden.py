@@ -125,6 +125,40 @@ def crafted_records():
     return out
 
 
+def tiling_episodes(records, tag, seed, walk_len=10, budget_s=120):
+    """The crafted tilings of tests/tiling_pools.py: per puzzle the walk along its first solution
+    (which carves the designed regions) and a walk of legal moves.  A record enters the pool only
+    if the reference walks its solution within budget_s seconds (its exact-fit search is unbounded,
+    SPaRC_Gym.py:736-853): the bound is applied here, so no test has to skip a case."""
+    import signal
+
+    class _Slow(Exception):
+        pass
+
+    def _alarm(*_):
+        raise _Slow()
+
+    kept = []
+    signal.signal(signal.SIGALRM, _alarm)
+    for r in records:
+        env = mg.make_env([r], traceback=True, max_steps=2000)
+        signal.alarm(budget_s)
+        try:
+            run_episode(env, copy.deepcopy(env.puzzles), 0, "solution0", np.random.default_rng(0), 40)
+            kept.append(r)
+        except _Slow:
+            print("dropped (the reference did not answer in time):", r["id"])
+        finally:
+            signal.alarm(0)
+    env = mg.make_env(kept, traceback=True, max_steps=2000)
+    pristine = copy.deepcopy(env.puzzles)
+    rng = np.random.default_rng(seed)
+    eps = [run_episode(env, pristine, i, "solution0", rng, 40) for i in range(len(kept))]
+    eps += [run_episode(env, pristine, i, "legal", rng, walk_len) for i in range(len(kept))]
+    return {"tag": tag, "traceback": True, "records": kept,
+            "processed": processed_full(mg.make_env(kept, traceback=True, max_steps=2000)), "episodes": eps}
+
+
 def main():
     mg.REFMOD = mg.import_reference()
     out = {}
@@ -137,6 +171,16 @@ def main():
     out["rules_mixed_tb0"] = episodes(rmix, False, strat, 28, 32, "rule-consistent mixed lattices")
     out["rules_random_tb1"] = episodes(rand7, True, strat, 20, 33, "random full-property 7x7")
     out["rules_crafted_tb1"] = episodes(crafted_records(), True, strat, 12, 34, "crafted audit edge cases")
+    sys.path.insert(0, os.path.dirname(HERE))
+    import tiling_pools
+    tp = tiling_pools.pools()
+    out["rules_tilings_tb1"] = tiling_episodes(tp["tilings"], "crafted tilings, 7x7 lattices and smaller", 35)
+    out["rules_tilings2w_tb1"] = tiling_episodes(tp["tilings2w"], "crafted tilings, lattices up to 11x11", 36)
+    # lattices up to 15x15, in two files (each within the size of the largest older golden file)
+    four = {half: [r for r in tp["tilings4w"] if (tiling_pools.category(r["id"]) in "abcde") == (half == "a")]
+            for half in "af"}
+    out["rules_tilings4w_tb1"] = tiling_episodes(four["a"], "crafted tilings, lattices up to 15x15, categories a-e", 37)
+    out["rules_tilings4wg_tb1"] = tiling_episodes(four["f"], "crafted tilings, lattices up to 15x15, categories f-h", 38)
     for k, v in out.items():
         path = os.path.join(HERE, f"{k}.json.gz")
         raw = json.dumps(v, separators=(",", ":")).encode()
