@@ -549,6 +549,103 @@ int sparc_rules_queue_stats(void *ctx, uint64_t *out);
  * to the following audits and the next sparc_load_rules, the budget to the next sparc_load_rules. */
 int sparc_set_rule_limits(void *ctx, uint32_t fit_cap_nodes, uint64_t table_entries);
 
+/* ---- depth-first subtree search of records with rule verdicts: exhaustive search without a frontier
+ * For each of M records (M >= 1, M < 2^31, independent of num_envs) the subtree of FORWARD moves
+ * below it is walked in pre-order under a node budget, in one launch and without touching an env:
+ * the context supplies its puzzle and rule tables, words, pitch and max_steps only, so
+ * sparc_load_puzzles + sparc_load_rules are enough (SPARC_E_STATE without rules) and no reset is
+ * needed.  Traceback contexts only: the record's direction stack is the search stack.
+ * The tree.  The root is record j's state.  A node's children are its legal actions
+ * (_get_legal_actions, SPaRC_Gym.py:1024-1051) without the traceback pop (the move back to path[-2],
+ * 1141-1166), in action order 0, 1, 2, 3: the walk is the lexicographic order of the action
+ * sequences.  A child is entered with one step() (1111-1238) as sparc_step_device takes it.  A node
+ * is a leaf when its step terminated (the agent is on the target, 1192: a TARGET leaf), when it
+ * truncated (max_steps, or no legal move, 1134 / 1195), or when it is live without a forward move (a
+ * DEAD END).  The root is never an entered node; a live root without a forward move is one dead end.
+ * Going back to a parent is not a step: a node at depth d below the root has step = root.step + d
+ * however much backtracking preceded it, and the walk never goes above the root's path length.
+ * Every record this call writes (cursor, first_sat, und_rec) is byte for byte what
+ * sparc_restore_device of the root, sparc_step_device with the forward actions from the root to that
+ * node and sparc_snapshot_device give (with more than one word: for a root whose stack fields at and
+ * above its top are zero, as after a reset and forward moves; the call writes those fields as zero).
+ * A target leaf is audited in place with the audit of sparc_rules_records_device (_validate_rules,
+ * 941-950).  A leaf whose bits carry SPARC_RULE_SEARCH_EXHAUSTED (its exact-fit search passed the
+ * node cap, or its puzzle's searches run on the host and no earlier answer is kept) is UNDECIDED:
+ * a target and, if its code was +100, listed, but neither satisfied nor unsatisfied; this call never
+ * pushes to the exact-fit queue and is never the "last audit call" of sparc_rules_finish.  Audit
+ * the records of und_rec with sparc_rules_records_device to decide them.
+ * Budget.  A record's walk enters at most `budget` (>= 1) nodes per call, finishes the accounting
+ * of the last one and stops there; k calls with budget B do exactly the first k * B nodes of the
+ * pre-order walk.  If no node is left after the last one the same call reports COMPLETE.
+ *  d_state   [M] uint32, in/out, non-NULL.  0: a fresh start, record j is the root.  Otherwise the
+ *            word a previous call wrote, and d_records[j] must be that call's cursor:
+ *              bits 0-7   the root's path length
+ *              bits 8-10  the next action to try at the cursor, 0..4
+ *              bit 28     SPARC_DFS_STATE_DONE     nothing is left to walk
+ *              bit 29     SPARC_DFS_STATE_FOUND    first_sat[j] has been written
+ *              bit 30     SPARC_DFS_STATE_LEAF     the cursor is an entered target leaf whose
+ *                                                  accounting is still owed (after an OVERFLOW)
+ *              bit 31     SPARC_DFS_STATE_STARTED  set by every call
+ *            A DONE word is left alone: status COMPLETE, nothing added, nothing written but the
+ *            status and the cursor (a copy of the record).
+ *  status    [M] uint8:
+ *              SPARC_DFS_INVALID   record j fails the checks of sparc_restore_device, names a puzzle
+ *                                  past the rule table, or its state word's root is longer than its
+ *                                  path: the cursor is zeroed, d_state[j] becomes DONE, its other
+ *                                  outputs are untouched, sparc_sync reports the error and every other
+ *                                  record is unaffected
+ *              SPARC_DFS_COMPLETE  the subtree is exhausted; the cursor is the root record again
+ *              SPARC_DFS_BUDGET    `budget` nodes entered and more are left; continue from the cursor
+ *              SPARC_DFS_PENDING   the root's last step ended its episode: no subtree, nothing
+ *                                  counted (d_state[j] becomes DONE)
+ *              SPARC_DFS_OVERFLOW  an undecided leaf did not fit und_rec; continue from the cursor
+ *  counts    [M][SPARC_DFS_COUNTERS] uint64, ACCUMULATED (the caller zeroes it): NODES forward moves
+ *            made, TARGETS target leaves, SATISFIED decided target leaves with SPARC_RULE_ALL, LISTED
+ *            target leaves whose step's code was +100, BOTH decided, satisfied and listed, DEAD_ENDS,
+ *            TRUNCATED, UNDECIDED.
+ *  cursor    [M] records, 16-B aligned; may be d_records itself.
+ *  first_sat [M] records or NULL; record j is written once, while FOUND is clear: as the walk is in
+ *            lexicographic order it is the least DECIDED satisfying path of root j.  The caller
+ *            zeroes the buffer: a zeroed record means none.
+ *  und_rec   [und_cap] records of undecided leaves, und_root [und_cap] the j each came from,
+ *            und_count a device counter, ACCUMULATED with 64-bit atomics (it may pass und_cap):
+ *            all three NULL (undecided leaves are only counted and no walk stops for them) or all
+ *            set.  A leaf that gets slot k >= und_cap stops its walk with OVERFLOW: the cursor is the
+ *            leaf, LEAF is set, the leaf is in NODES but in no other counter, and the next call
+ *            accounts for it first without counting the node again (reset und_count before it).
+ *            The order of the entries is not defined.
+ * info must match the context as for sparc_expand_device (SPARC_E_INVALID naming the field); every
+ * other argument is checked before any launch (SPARC_E_INVALID naming it).  Device pointers,
+ * asynchronous on the context's stream. */
+#define SPARC_DFS_INVALID 0
+#define SPARC_DFS_COMPLETE 1
+#define SPARC_DFS_BUDGET 2
+#define SPARC_DFS_PENDING 3
+#define SPARC_DFS_OVERFLOW 4
+#define SPARC_DFS_STATE_DONE (1u << 28)
+#define SPARC_DFS_STATE_FOUND (1u << 29)
+#define SPARC_DFS_STATE_LEAF (1u << 30)
+#define SPARC_DFS_STATE_STARTED (1u << 31)
+enum { SPARC_DFS_NODES, SPARC_DFS_TARGETS, SPARC_DFS_SATISFIED, SPARC_DFS_LISTED, SPARC_DFS_BOTH,
+       SPARC_DFS_DEAD_ENDS, SPARC_DFS_TRUNCATED, SPARC_DFS_UNDECIDED, SPARC_DFS_COUNTERS };
+typedef struct {
+    uint8_t *status;
+    uint64_t *counts;
+    void *cursor;
+    void *first_sat;
+    void *und_rec;
+    uint32_t *und_root;
+    uint64_t *und_count;
+    uint64_t und_cap;
+} sparc_dfs_out;
+int sparc_dfs_device(void *ctx, const sparc_snapshot_info *info, const void *d_records, int64_t M,
+                     uint32_t budget, uint32_t *d_state, const sparc_dfs_out *out);
+/* the host-pointer form (records, state and every member of out on the host, no alignment
+ * requirement): staged through the context's stream, returns after the data have moved; state,
+ * counts and und_count are read, updated and written back, first_sat is read and written back */
+int sparc_dfs_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
+                   uint32_t budget, uint32_t *state, const sparc_dfs_out *out);
+
 /* ---- debug: kernel variants (A/B runs and tests) ----------------------------------------------
  * Selects, for this context, among kernel variants that compute identical results.  Callers never
  * need it, and nothing else (no environment variable) changes the kernel a context runs.

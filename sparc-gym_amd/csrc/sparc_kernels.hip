@@ -11,6 +11,7 @@
 //   k_snapshot / k_restore  the state as per-env records and back  (sparc_snapshot.hpp)
 //   k_rules_rec  rule audit of state records, without an env      (sparc_rules_rec.hpp)
 //   k_playout  K legal-move playouts of each state record, without an env (sparc_playout.hpp)
+//   k_dfs      depth-first subtree search of state records with rule verdicts (sparc_dfs.hpp)
 // No MFMA: this is integer / bitboard work, bound by latency and HBM.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -35,6 +36,7 @@
 #include "sparc_expand.hpp"
 #include "sparc_playout.hpp"
 #include "sparc_rules_rec.hpp"
+#include "sparc_dfs.hpp"
 #include "sparc_devbuf.hpp"
 #include "sparc_tables.hpp"
 #include "sparc_gym_amd.h"
@@ -2041,6 +2043,10 @@ struct Ctx {
     // sparc_playout_host (sparc_playout.hpp): the per-playout outputs and the trace, the stats
     DevBuf<uint8_t> po_out;
     DevBuf<int32_t> po_stats;
+    // sparc_dfs_host (sparc_dfs.hpp): cursor | first_sat records, the undecided records, and
+    // counts [8M] | und_count | state [M] | und_root [cap] | status [M]
+    DevBuf<uint8_t> df_rec, df_und;
+    DevBuf<uint64_t> df_out;
     DevBuf<uint16_t> s_bits;        // per-env audit outputs of the host-pointer / one-env calls
     DevBuf<uint8_t> s_region;
     DevBuf<uint64_t> s_fit;
@@ -3672,6 +3678,122 @@ int sparc_playout_host(void* ctx, const sparc_snapshot_info* info, const void* r
         HIPCHK(c, hipMemcpyAsync(out->final_rec, d.final_rec, (size_t)info->record_bytes * mk, hipMemcpyDeviceToHost,
                                  c->stream));
     if (out->stats) HIPCHK(c, hipMemcpyAsync(out->stats, d.stats, 64 * m, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
+}
+
+// ---- depth-first subtree search of records (sparc_dfs.hpp): reads the context's tables only
+static int check_dfs_args(Ctx* c, const sparc_snapshot_info* info, const void* records, int64_t M, uint32_t budget,
+                          const uint32_t* state, const sparc_dfs_out* out, bool device) {
+    if (!c->rules) return fail(c, SPARC_E_STATE, "sparc_load_rules has not been called");
+    int rc = check_snapshot_info(c, info);
+    if (rc) return rc;
+    if (!c->cfg.traceback)
+        return fail(c, SPARC_E_INVALID,
+                    "sparc_dfs_device needs a traceback context: the record's direction stack is the search stack");
+    if (!records) return fail(c, SPARC_E_INVALID, "null records");
+    if (!state) return fail(c, SPARC_E_INVALID, "null state");
+    if (!out) return fail(c, SPARC_E_INVALID, "null out");
+    if (!out->status) return fail(c, SPARC_E_INVALID, "null out->status");
+    if (!out->counts) return fail(c, SPARC_E_INVALID, "null out->counts");
+    if (!out->cursor) return fail(c, SPARC_E_INVALID, "null out->cursor");
+    if (M < 1 || M > 0x7FFFFFFFll) return fail(c, SPARC_E_INVALID, "M must be in 1..2^31-1");
+    if (budget < 1) return fail(c, SPARC_E_INVALID, "budget must be at least 1");
+    const int und = (out->und_rec != nullptr) + (out->und_root != nullptr) + (out->und_count != nullptr);
+    if (und != 0 && und != 3)
+        return fail(c, SPARC_E_INVALID, "out->und_rec, out->und_root and out->und_count must be all NULL or all set");
+    if (device) {
+        if ((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(out->cursor) |
+             reinterpret_cast<uintptr_t>(out->first_sat) | reinterpret_cast<uintptr_t>(out->und_rec)) & 15u)
+            return fail(c, SPARC_E_INVALID,
+                        "records, out->cursor, out->first_sat and out->und_rec must be 16-B aligned");
+        if ((reinterpret_cast<uintptr_t>(out->counts) | reinterpret_cast<uintptr_t>(out->und_count)) & 7u)
+            return fail(c, SPARC_E_INVALID, "out->counts and out->und_count must be 8-B aligned");
+        if ((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(out->und_root)) & 3u)
+            return fail(c, SPARC_E_INVALID, "state and out->und_root must be 4-B aligned");
+    }
+    return SPARC_OK;
+}
+
+int sparc_dfs_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M, uint32_t budget,
+                     uint32_t* d_state, const sparc_dfs_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_dfs_args(c, info, d_records, M, budget, d_state, out, true))) return rc;
+    const Params p = make_params(c);
+    const RulesTab rt = rules_tab(c, c->rl, false);   // no exact-fit queue: such leaves are undecided
+    const DfsOut o{out->status,
+                   reinterpret_cast<unsigned long long*>(out->counts),
+                   static_cast<uint4*>(out->cursor),
+                   static_cast<uint4*>(out->first_sat),
+                   static_cast<uint4*>(out->und_rec),
+                   out->und_root,
+                   reinterpret_cast<unsigned long long*>(out->und_count),
+                   out->und_cap};
+    const uint4* rec = static_cast<const uint4*>(d_records);
+    const uint32_t m = (uint32_t)M;
+    const dim3 gr((unsigned)(((uint64_t)M + kSnapBlock - 1) / kSnapBlock));
+    auto go = [&](auto kern) { kern<<<gr, kSnapBlock, 0, c->stream>>>(p, rt, rec, m, budget, d_state, o); };
+    // the table-only audit when every puzzle has a region-code table, as launch_rules chooses it
+    if (c->W == 1 && c->rl.tab_all) go(k_dfs<1, true>);
+    else if (c->W == 1) go(k_dfs<1, false>);
+    else if (c->W == 2) go(k_dfs<2, false>);
+    else go(k_dfs<4, false>);
+    return launch_check(c);
+}
+
+int sparc_dfs_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M, uint32_t budget,
+                   uint32_t* state, const sparc_dfs_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_dfs_args(c, info, records, M, budget, state, out, false))) return rc;
+    const size_t m = (size_t)M, rb = (size_t)info->record_bytes, bytes = rb * m;
+    const size_t cap = out->und_rec ? (size_t)out->und_cap : 0;
+    // u64 words: counts [8m] | und_count | then state [m] u32, und_root [cap] u32, status [m] u8
+    const size_t w_state = 8 * m + 1, w_root = w_state + (m + 1) / 2, w_status = w_root + (cap + 1) / 2,
+                 words = w_status + (m + 7) / 8;
+    HIPCHK(c, c->fk_rec.reserve(bytes));
+    HIPCHK(c, c->df_rec.reserve(2 * bytes));
+    HIPCHK(c, c->df_out.reserve(words));
+    if (out->und_rec) HIPCHK(c, c->df_und.reserve(rb * (cap ? cap : 1)));   // (no entries: every undecided leaf overflows)
+    uint64_t* o64 = c->df_out.get();
+    sparc_dfs_out d{};
+    d.counts = o64;
+    d.und_count = out->und_rec ? o64 + 8 * m : nullptr;
+    uint32_t* d_state = reinterpret_cast<uint32_t*>(o64 + w_state);
+    d.und_root = out->und_rec ? reinterpret_cast<uint32_t*>(o64 + w_root) : nullptr;
+    d.status = reinterpret_cast<uint8_t*>(o64 + w_status);
+    d.cursor = c->df_rec.get();
+    d.first_sat = out->first_sat ? c->df_rec.get() + bytes : nullptr;
+    d.und_rec = out->und_rec ? c->df_und.get() : nullptr;
+    d.und_cap = out->und_cap;
+    HIPCHK(c, hipMemcpyAsync(c->fk_rec.get(), records, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d.counts, out->counts, 64 * m, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_state, state, 4 * m, hipMemcpyHostToDevice, c->stream));
+    if (d.und_count) HIPCHK(c, hipMemcpyAsync(d.und_count, out->und_count, 8, hipMemcpyHostToDevice, c->stream));
+    if (d.first_sat) HIPCHK(c, hipMemcpyAsync(d.first_sat, out->first_sat, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = sparc_dfs_device(c, info, c->fk_rec.get(), M, budget, d_state, &d))) return rc;
+    HIPCHK(c, hipMemcpyAsync(out->status, d.status, m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->counts, d.counts, 64 * m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(state, d_state, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->cursor, d.cursor, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d.first_sat) HIPCHK(c, hipMemcpyAsync(out->first_sat, d.first_sat, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d.und_count) {
+        // the entries this call stored: slots old count .. min(new count, cap)
+        uint64_t before = *out->und_count;
+        HIPCHK(c, hipMemcpyAsync(out->und_count, d.und_count, 8, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = sparc_sync(c))) return rc;
+        const uint64_t after = *out->und_count < out->und_cap ? *out->und_count : out->und_cap;
+        if (before < after) {
+            const size_t k0 = (size_t)before, nk = (size_t)(after - before);
+            HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(out->und_rec) + rb * k0, c->df_und.get() + rb * k0, rb * nk,
+                                     hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(out->und_root + k0, d.und_root + k0, 4 * nk, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
     return sparc_sync(c);
 }
 

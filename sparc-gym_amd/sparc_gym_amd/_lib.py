@@ -74,6 +74,22 @@ class SparcPlayoutOut(ctypes.Structure):
                                         "stats")]
 
 
+# SPARC_DFS_*: the status of a record's walk after sparc_dfs_device
+DFS_INVALID, DFS_COMPLETE, DFS_BUDGET, DFS_PENDING, DFS_OVERFLOW = range(5)
+# the columns of its counters
+(DFS_NODES, DFS_TARGETS, DFS_SATISFIED, DFS_LISTED, DFS_BOTH, DFS_DEAD_ENDS, DFS_TRUNCATED, DFS_UNDECIDED,
+ DFS_COUNTERS) = range(9)
+DFS_COUNTER_NAMES = ("nodes", "targets", "satisfied", "listed", "both", "dead_ends", "truncated", "undecided")
+# SPARC_DFS_STATE_*: bits of the state word (bits 0-7: the root's path length, 8-10: the next action)
+DFS_STATE_DONE, DFS_STATE_FOUND, DFS_STATE_LEAF, DFS_STATE_STARTED = 1 << 28, 1 << 29, 1 << 30, 1 << 31
+
+
+class SparcDfsOut(ctypes.Structure):
+    """sparc_dfs_out: the outputs of sparc_dfs_device / _host."""
+    _fields_ = [(k, c_void_p) for k in ("status", "counts", "cursor", "first_sat", "und_rec", "und_root",
+                                        "und_count")] + [("und_cap", c_uint64)]
+
+
 _SIGS = {
     "sparc_abi_version": ([], c_int32),
     "sparc_last_error": ([c_void_p], ctypes.c_char_p),
@@ -123,6 +139,10 @@ _SIGS = {
                               c_uint64, c_uint64, ctypes.c_uint32, ctypes.POINTER(SparcPlayoutOut)], c_int32),
     "sparc_playout_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_int32, c_int32,
                             c_uint64, c_uint64, ctypes.c_uint32, ctypes.POINTER(SparcPlayoutOut)], c_int32),
+    "sparc_dfs_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, ctypes.c_uint32,
+                          c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
+    "sparc_dfs_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, ctypes.c_uint32,
+                        c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
     "sparc_load_rules": ([c_void_p, ctypes.POINTER(SparcRulesTable)], c_int32),
     "sparc_rules_device": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_rules_host": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),

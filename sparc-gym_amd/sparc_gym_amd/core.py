@@ -363,6 +363,61 @@ class SparcCore:
                                                 ctypes.byref(o)))
         return out
 
+    # ---------------------------------------------------------------- depth-first subtree search of records
+    def dfs_device(self, info, d_records, M, budget, d_state, d_status, d_counts, d_cursor, d_first=None,
+                   d_und_rec=None, d_und_root=None, d_und_count=None, und_cap=0):
+        """sparc_dfs_device: the forward-move subtree below each of M records, walked depth-first
+        for at most ``budget`` nodes each, with the rule verdict of every target leaf; state [M]
+        uint32 in/out, status [M] uint8, counts [M][8] uint64 accumulated, cursor [M] records,
+        optionally first [M] records and the undecided leaves' buffer (all three pointers or none);
+        reads the context's tables only (asynchronous)."""
+        M, budget = int(M), int(budget)
+        if not 1 <= budget < 2**32:
+            raise ValueError("budget must be in 1..2^32-1")
+        out = _lib.SparcDfsOut(d_status, d_counts, d_cursor, d_first, d_und_rec, d_und_root, d_und_count, int(und_cap))
+        self._check(self.lib.sparc_dfs_device(self.ctx, ctypes.byref(info), d_records, M, budget, d_state,
+                                              ctypes.byref(out)))
+
+    def dfs_host(self, info, records, budget, state=None, counts=None, first=None, undecided=0):
+        """Walk host records [M, record_bytes] (synchronous): a dict of host arrays ``status`` [M]
+        uint8, ``counts`` [M, 8] uint64, ``cursor`` and ``first`` [M, record_bytes] uint8, ``state``
+        [M] uint32 and, with ``undecided`` > 0 (the buffer's entries), ``undecided``
+        [n, record_bytes] uint8, ``undecided_root`` [n] uint32 and ``undecided_total``.  ``state``,
+        ``counts`` and ``first`` of a previous call are continued in place (``records`` is then that
+        call's ``cursor``); fresh zeroed arrays otherwise."""
+        rec = np.ascontiguousarray(records, np.uint8)
+        if rec.ndim != 2 or rec.shape[1] != info.record_bytes or len(rec) < 1:
+            raise ValueError(f"records must be [M, {info.record_bytes}] uint8 with M >= 1")
+        M, budget, cap = len(rec), int(budget), int(undecided)
+        if not 1 <= budget < 2**32:
+            raise ValueError("budget must be in 1..2^32-1")
+        if cap < 0:
+            raise ValueError("undecided must not be negative")
+
+        def arg(a, shape, dtype, what):
+            if a is None:
+                return np.zeros(shape, dtype)
+            if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError(f"{what} must be a C-contiguous {np.dtype(dtype).name} array {list(shape)}")
+            return a
+
+        state = arg(state, (M,), np.uint32, "state")
+        counts = arg(counts, (M, _lib.DFS_COUNTERS), np.uint64, "counts")
+        first = arg(first, rec.shape, np.uint8, "first")
+        out = {"status": np.empty(M, np.uint8), "counts": counts, "cursor": np.empty_like(rec), "first": first,
+               "state": state}
+        und = np.empty((cap, rec.shape[1]), np.uint8) if cap else None
+        root = np.empty(cap, np.uint32) if cap else None
+        count = np.zeros(1, np.uint64) if cap else None
+        o = _lib.SparcDfsOut(_ptr(out["status"]), _ptr(counts), _ptr(out["cursor"]), _ptr(first), _ptr(und),
+                             _ptr(root), _ptr(count), cap)
+        self._check(self.lib.sparc_dfs_host(self.ctx, ctypes.byref(info), _ptr(rec), M, budget, _ptr(state),
+                                            ctypes.byref(o)))
+        if cap:
+            n = min(int(count[0]), cap)
+            out.update(undecided=und[:n], undecided_root=root[:n], undecided_total=int(count[0]))
+        return out
+
 
 def visited_planes(bits, table: PuzzleTable, x_dim=None, y_dim=None):
     """Decode visited bitboards [words][N] into int32 planes [N][x_dim][y_dim] (host)."""

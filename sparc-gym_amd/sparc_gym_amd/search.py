@@ -11,6 +11,11 @@ The compaction is plain torch indexing on the GPU (``nonzero`` + a row gather); 
 ascending child index, parent-major then action, so every result is deterministic.  Not done
 here: detecting the same position reached twice within a frontier, and compaction inside the
 kernel.
+
+``solve_dfs`` needs neither a frontier per level nor a compaction: after a few split levels it
+hands every node to ``SPaRCVecEnv.dfs``, which walks the subtree below it depth-first on the GPU
+(the record's direction stack is the search stack) and returns counters, so its memory does not
+depend on the tree.
 """
 from __future__ import annotations
 
@@ -180,6 +185,132 @@ def monte_carlo(vec, snap, playouts, horizon, seed=0, forward_only=None):
         solution[j] = [int(a) for a in trace[:nsteps[j, k], j, k]]
     return {"visits": visits, "wins": wins, "losses": losses, "mean_steps": mean_steps, "best_action": best,
             "solution": solution}
+
+
+def solve_dfs(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, undecided=65536):
+    """Every self-avoiding path from the start of each of ``puzzle_indices`` (one root per entry:
+    that puzzle's reset state, all roots at once) counted with the puzzle's own verdict, as
+    ``solve_by_rules`` finds them, but depth-first on the GPU (``vec.dfs``, k_dfs): the memory does
+    not grow with the tree, so lattices whose levels no frontier can hold are searched too.
+
+    *Split*: forward-only levels of ``expand_frontier`` (the pops dropped, as in ``solve_by_rules``)
+    until the frontier holds at least ``min_roots`` nodes or is empty; target nodes met on the way
+    are audited with ``vec.audit_records``, dead ends and truncations counted.  *Search*:
+    ``vec.dfs`` on the whole frontier with ``budget`` nodes per sub-root and launch, until every
+    sub-root is done or, with ``max_nodes`` (anytime mode), the nodes entered reach it.  After each
+    launch the undecided leaves (exact fits past the GPU's node cap; at most ``undecided`` stored
+    per launch, walks that did not fit resume at their leaf) are judged by ``vec.audit_records``,
+    which finishes them on the host, and their verdicts added.  ``undecided=0``: such leaves stay
+    in the ``undecided`` counter.
+
+    Needs a traceback env with ``max_steps`` at least the lattice's points (ValueError), at least
+    ``len(puzzle_indices)`` envs, and overwrites the env state (the roots come from ``vec.reset``).
+
+    Returns a dict, index r: ``puzzle_indices[r]``: ``nodes``, ``targets``, ``satisfied``,
+    ``listed``, ``both``, ``dead_ends``, ``truncated``, ``undecided`` int64 [R] (the counters of
+    ``vec.dfs`` over the whole tree of root r), ``complete`` [R] bool, ``solution``: the
+    lexicographically least satisfying action list from the puzzle's start found so far, or None
+    (final when ``complete``), ``launches``: the ``vec.dfs`` calls made, and ``sub_roots``: the
+    frontier the search started from."""
+    from . import _lib
+    q = np.asarray(puzzle_indices, np.int64)
+    R = len(q)
+    if q.ndim != 1 or R < 1 or R > vec.num_envs:
+        raise ValueError(f"puzzle_indices must hold 1..{vec.num_envs} puzzle indices")
+    if not vec.traceback:
+        raise ValueError("solve_dfs needs a traceback env: the record's direction stack is the search stack")
+    points = max(int(vec.puzzles[int(k)]["x_size"]) * int(vec.puzzles[int(k)]["y_size"]) for k in q)
+    if vec.max_steps < points:
+        raise ValueError(f"max_steps = {vec.max_steps} is below the lattice's {points} points: paths would be "
+                         "truncated")
+    full = np.full(vec.num_envs, q[0], np.int64)
+    full[:R] = q
+    vec.reset(options={"puzzle_index": full})
+    frontier = vec.snapshot(envs=np.arange(R))
+    dev = frontier.records.device
+    root = torch.arange(R, device=dev)
+    C = _lib.DFS_COUNTERS
+    total = torch.zeros((R, C), dtype=torch.int64, device=dev)
+    best = [None] * R
+
+    def add(col, roots, weight=None):
+        if len(roots):
+            total[:, col] += torch.bincount(roots, weights=weight, minlength=R).to(torch.int64)
+
+    def offer(snap, roots):                               # satisfying leaves: candidates for the solution
+        for r, m in zip(roots.cpu().numpy(), snap.moves()):
+            if best[int(r)] is None or m < best[int(r)]:
+                best[int(r)] = m
+
+    def judge(snap, roots, listed):                       # final verdicts of target records
+        bits = vec.audit_records(snap)["bits"].to(torch.int64) & 0xFFFF
+        sat = (bits & RULE_ALL) != 0
+        add(_lib.DFS_SATISFIED, roots[sat])
+        add(_lib.DFS_BOTH, roots[sat & listed])
+        rows = sat.nonzero().squeeze(1)
+        if len(rows):
+            offer(snap.select(rows), roots[rows])
+
+    # ---- split: forward-only breadth-first levels
+    while 0 < len(frontier) < min_roots:
+        out = expand_frontier(vec, frontier)              # the frontier holds live nodes only
+        children, parent = out["children"], out["parent"]
+        code, flags = out["reward_code"], out["flags"]
+        if len(children):                                 # drop the pops: one point shorter than the parent
+            fwd = children.fields()["path_len"] > frontier.fields()["path_len"][parent]
+            keep = fwd.nonzero().squeeze(1)
+            children, parent, code, flags = children.select(keep), parent[keep], code[keep], flags[keep]
+        kids = torch.bincount(parent, minlength=len(frontier))
+        add(_lib.DFS_DEAD_ENDS, root[kids == 0])          # live without a forward move
+        if len(children) == 0:
+            frontier = children
+            root = root[:0]
+            break
+        croot = root[parent]
+        add(_lib.DFS_NODES, croot)
+        term = (flags & TERMINATED) != 0
+        rows = term.nonzero().squeeze(1)
+        if len(rows):
+            listed = code[rows] == 100
+            add(_lib.DFS_TARGETS, croot[rows])
+            add(_lib.DFS_LISTED, croot[rows][listed])
+            judge(children.select(rows), croot[rows], listed)
+        add(_lib.DFS_TRUNCATED, croot[((flags & DONE_BITS) != 0) & ~term])
+        live = ((flags & DONE_BITS) == 0).nonzero().squeeze(1)
+        frontier = children.select(live)
+        root = croot[live]
+    # ---- search: depth-first below every node of the frontier
+    M = len(frontier)
+    complete = np.ones(R, np.bool_)
+    launches = 0
+    if M:
+        cur, state, counts, first = frontier, None, None, None
+        resolved = torch.zeros(M, dtype=torch.int64, device=dev)
+        split_nodes = int(total[:, _lib.DFS_NODES].sum())
+        while True:
+            out = vec.dfs(cur, budget, state=state, counts=counts, first=first, undecided=undecided)
+            launches += 1
+            cur, state, counts, first = out["cursor"], out["state"], out["counts"], out["first"]
+            if undecided and len(out["undecided"]):
+                und, sub = out["undecided"], out["undecided_root"]
+                aux = und.records[:, 4:8].to(torch.int64)
+                listed = ((aux[:, 2] & 3) == 1)           # outcome +1: the step's code was +100
+                judge(und, root[sub], listed)
+                resolved += torch.bincount(sub, minlength=M)
+            if bool(out["done"].all()):
+                break
+            if max_nodes is not None and split_nodes + int(counts[:, _lib.DFS_NODES].sum()) >= max_nodes:
+                break
+        total.index_add_(0, root, counts)
+        add(_lib.DFS_UNDECIDED, root, -resolved.to(torch.float64))
+        found = out["found"].nonzero().squeeze(1)
+        if len(found):
+            offer(first.select(found), root[found])
+        open_roots = root[~out["done"]].cpu().numpy()
+        complete[open_roots] = False
+    res = {name: total[:, k].cpu().numpy() for k, name in enumerate(_lib.DFS_COUNTER_NAMES)}
+    res.update(complete=complete, solution=best, launches=launches, sub_roots=M)
+    return res
 
 
 def solve_by_rules(vec, puzzle_indices, max_frontier=1 << 22):

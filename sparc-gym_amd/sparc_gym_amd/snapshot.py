@@ -111,6 +111,26 @@ class Snapshot:
         return {"x": pos & 0xFF, "y": (pos >> 8) & 0xFF, "path_len": (pos >> 16) & 0xFF, "step": w[:, 2],
                 "puzzle_index": w[:, 3]}
 
+    def moves(self):
+        """The action lists of traceback records: per record the first ``path_len - 1`` moves of its
+        direction stack, the path from the puzzle's start as actions (0 right, 1 up, 2 left, 3
+        down).  Move k sits at bits ``2 * (k % 32)`` of stack word ``k // 32``, the stack follows the
+        ``words`` u64 of the visited board; fields at and above the top (stale with more than one
+        word) are not read.  A list of lists of ints, on the host (GPU records are copied); a
+        zeroed record (path length 0) gives an empty list.  ValueError on records without
+        traceback: they hold no moves."""
+        if not self.info.traceback:
+            raise ValueError("only traceback records hold the path's moves")
+        rec = self.numpy()
+        W = int(self.info.words)
+        if len(rec) == 0:
+            return []
+        n = ((rec[:, :4].copy().view("<u4")[:, 0] >> 16) & 0xFF).astype(np.int64)
+        stack = np.ascontiguousarray(rec[:, 16 + 8 * W:16 + 24 * W]).view("<u8")          # [M, 2W]
+        k = np.arange(64 * W)
+        field = ((stack[:, k // 32] >> (2 * (k % 32)).astype(np.uint64)) & np.uint64(3)).astype(np.int64)
+        return [[int(a) for a in field[j, :max(int(n[j]) - 1, 0)]] for j in range(len(rec))]
+
     # ------------------------------------------------------------------ frontiers
     def select(self, idx):
         """A new ``Snapshot`` of rows ``idx``: a tensor, array or list of integers (any order,

@@ -632,6 +632,86 @@ class SPaRCVecEnv:
         self.core.rules_finish(out["bits"].data_ptr(), d_fit)   # rec lives until here: the re-run reads it
         return out
 
+    def dfs(self, snap, budget, state=None, counts=None, first=None, undecided=0):
+        """Depth-first search of the forward-move subtree below every record of ``snap`` (M of
+        them), at most ``budget`` entered nodes per record and call, in one launch and without
+        changing or reading any env (k_dfs).  A node's children are its legal actions without the
+        traceback pop, in action order; a node that reached the target is audited where it stands
+        (the audit of ``audit_records``), and only counters, a cursor and a few records come back,
+        so the memory does not depend on the tree.  Traceback envs only (ValueError otherwise): the
+        record's direction stack is the search stack.  Loads the rules on first use; needs no reset.
+
+        To continue, pass the returned ``cursor`` as ``snap`` together with the returned ``state``,
+        ``counts`` and ``first`` (updated in place).  k calls of budget B do exactly the first k * B
+        nodes of each record's pre-order walk.
+
+        Returns a dict of GPU tensors / Snapshots: ``status`` [M] uint8 (``_lib.DFS_*``: 0 bad
+        record, 1 complete, 2 budget spent, 3 the record was already done, 4 the undecided buffer
+        overflowed), ``counts`` [M, 8] int64 accumulated (columns ``_lib.DFS_COUNTER_NAMES``),
+        ``cursor`` (Snapshot: where each walk stands; the root again when complete), ``state`` [M]
+        int32, ``first`` (Snapshot: the lexicographically least decided satisfying leaf, zeroed where
+        none yet), ``found`` and ``done`` [M] bool.  A target leaf whose exact-fit search passed the
+        GPU's node cap is *undecided*: counted, not judged.  With ``undecided`` > 0 (the buffer's
+        entries) those leaves come back too, to be judged by ``audit_records``: ``undecided``
+        (Snapshot of the n stored ones), ``undecided_root`` [n] int64 (their rows of ``snap``) and
+        ``undecided_total`` int; a walk whose leaf did not fit stops with status 4 and resumes at
+        that leaf.  A record that fails the kernel's checks gets status 0 and a zeroed cursor, and
+        the next ``core.sync()`` raises."""
+        from .snapshot import Snapshot, info_mismatch
+        self._stream()
+        if not self.traceback:
+            raise ValueError("dfs needs a traceback env: the record's direction stack is the search stack")
+        bad = info_mismatch(snap.info, self.core.snapshot_info())
+        if bad is not None:
+            raise ValueError(f"snapshot does not match this env: {bad} differs")
+        self._load_rules()
+        M, budget, cap = len(snap), int(budget), int(undecided)
+        if M < 1 or M >= 2**31:
+            raise ValueError("a snapshot of 1 .. 2^31 - 1 records is needed")
+        if not 1 <= budget < 2**32:
+            raise ValueError("budget must be in 1..2^32-1")
+        if cap < 0:
+            raise ValueError("undecided must not be negative")
+        dev, rb = self.device, snap.info.record_bytes
+        rec = snap.records
+        if not isinstance(rec, torch.Tensor):
+            rec = torch.from_numpy(np.ascontiguousarray(rec, np.uint8))
+        rec = rec.to(dev).contiguous()
+
+        def arg(a, shape, dtype, what):
+            if a is None:
+                return torch.zeros(shape, dtype=dtype, device=dev)
+            if isinstance(a, Snapshot):
+                a = a.records
+            if not (isinstance(a, torch.Tensor) and a.dtype == dtype and tuple(a.shape) == shape and
+                    a.is_contiguous() and a.device == dev):
+                raise ValueError(f"{what} must be a contiguous {dtype} tensor {list(shape)} on {dev}")
+            return a
+
+        state = arg(state, (M,), torch.int32, "state")
+        counts = arg(counts, (M, _lib.DFS_COUNTERS), torch.int64, "counts")
+        first = arg(first, (M, rb), torch.uint8, "first")
+        status = torch.empty(M, dtype=torch.uint8, device=dev)
+        cursor = torch.empty((M, rb), dtype=torch.uint8, device=dev)
+        und = root = count = None
+        if cap:
+            und = torch.empty((cap, rb), dtype=torch.uint8, device=dev)
+            root = torch.empty(cap, dtype=torch.int32, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.core.dfs_device(snap.info, rec.data_ptr(), M, budget, state.data_ptr(), status.data_ptr(),
+                             counts.data_ptr(), cursor.data_ptr(), first.data_ptr(),
+                             und.data_ptr() if cap else None, root.data_ptr() if cap else None,
+                             count.data_ptr() if cap else None, cap)
+        out = {"status": status, "counts": counts, "cursor": Snapshot(cursor, snap.info), "state": state,
+               "first": Snapshot(first, snap.info), "found": (state & _lib.DFS_STATE_FOUND) != 0,
+               "done": (state & _lib.DFS_STATE_DONE) != 0}
+        if cap:
+            total = int(count.item())
+            n = min(total, cap)
+            out.update(undecided=Snapshot(und[:n], snap.info), undecided_root=root[:n].to(torch.int64),
+                       undecided_total=total)
+        return out
+
     def state(self):
         """Host snapshot of the per-env state (x, y, path_len, step, puzzle, outcome, visited bits)."""
         torch.cuda.current_stream(self.device).synchronize()
