@@ -141,7 +141,20 @@ const char *sparc_last_error(const void *ctx);
 int sparc_create(int device, const sparc_config *cfg, void **ctx_out);
 int sparc_destroy(void *ctx);
 /* run on this HIP stream (hipStream_t as void*; NULL = the HIP null stream).  A new context
- * runs on its own non-blocking stream; sparc_use_own_stream() returns to it. */
+ * runs on its own non-blocking stream; sparc_use_own_stream() returns to it.
+ * The stream contract (tests/test_gpu_streams.py):
+ *  - every launch and copy of a call goes to the context's current stream, in call order; a call
+ *    marked asynchronous returns without waiting for work already on that stream, and the `*_host`
+ *    forms, sparc_rules_finish, sparc_read_state, sparc_env_* and sparc_sync wait for that stream and
+ *    for no other non-blocking stream (sparc_sync and the exact-fit queue's host finish also make
+ *    blocking null-stream copies, which wait for every stream not created hipStreamNonBlocking:
+ *    DESIGN.md);
+ *  - sparc_set_stream / sparc_use_own_stream only change where the NEXT calls go: they insert no
+ *    dependency between the old stream and the new one and wait for nothing;
+ *  - the caller orders the two streams (an event wait, or a synchronisation of the old one) before
+ *    the first call on the new one.  The context's state and its scratch (staged actions and
+ *    indices, fork and playout records, the exact-fit queue, ...) are reused from call to call and
+ *    are ordered by that hand-over and by nothing else; two contexts share no device memory. */
 int sparc_set_stream(void *ctx, void *stream);
 int sparc_use_own_stream(void *ctx);
 int sparc_sync(void *ctx);

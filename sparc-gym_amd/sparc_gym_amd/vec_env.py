@@ -254,6 +254,7 @@ class SPaRCVecEnv:
         reset: env i -> i mod P (the vector form of __init__ loading puzzle 0, SPaRC_Gym.py:90)."""
         if not self.core.has_state:
             return self._cursor.copy()
+        self._stream()   # the copy below and the read after it run on the caller's current stream
         cur = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
         self.core.copy_state_device(4, cur.data_ptr())
         return cur.cpu().numpy().astype(np.int64)
@@ -714,7 +715,7 @@ class SPaRCVecEnv:
 
     def state(self):
         """Host snapshot of the per-env state (x, y, path_len, step, puzzle, outcome, visited bits)."""
-        torch.cuda.current_stream(self.device).synchronize()
+        self._stream()   # read_state copies on the context's stream and synchronises it
         return self.core.read_state()
 
     def close(self):

@@ -36,6 +36,7 @@ def _yardstick(v, snap, K, L, seed=0, id0=0, forward=False):
     M = len(snap)
     MK = M * K
     g = np.arange(MK)
+    ids = np.uint64(int(id0) & (2**64 - 1)) + g.astype(np.uint64)   # id0 is a 64-bit counter: it may pass 2^63
     cur = snap.select(g // K).numpy()
     live = ~_pending(cur)
     end = np.where(live, _lib.END_HORIZON, _lib.END_PENDING)
@@ -56,7 +57,7 @@ def _yardstick(v, snap, K, L, seed=0, id0=0, forward=False):
         dead = live & (mask == 0) & (legal != 0)
         end[dead] = _lib.END_DEAD_END
         live = live & ~dead
-        a = rand_pick(seed, id0 + g, t, mask)
+        a = rand_pick(seed, ids, t, mask)
         c = out["reward_code"].cpu().numpy()[g, a].astype(np.int64)
         f = out["flags"].cpu().numpy()[g, a].astype(np.int64)
         child = out["children"].records.cpu().numpy()[4 * g + a]
