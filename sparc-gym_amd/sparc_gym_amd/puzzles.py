@@ -164,8 +164,12 @@ def lattice_geometry(puzzles, pitch=None, words=None):
     """Bitboard geometry (pitch, words, x_max, y_max) for a pool.
 
     words == 1 is the PADDED 64-bit layout of the kernel's fast path: pitch > y_max (a blocked
-    column) and (x_max + 1) * pitch <= 64 (a blocked row), pitch <= 15 — every 7x7 or 5x5
-    pool.  Larger lattices use 2 or 4 words with pitch >= y_max and explicit bounds checks.
+    column) and (x_max + 1) * pitch <= 64 (a blocked row), pitch <= 15 — every pool up to 7x7,
+    and also the strips and short wide boards 3x9 .. 3x13 (pitch 10 .. 14), 5x9 (pitch 10), 9x5
+    (pitch 6) and 9x3 .. 15x3 (pitch 4; 15x3 fills all 64 bits).  Larger lattices use 2 or 4 words
+    with pitch >= y_max and explicit bounds checks.  Over the single-size pools of 1 .. 7 cells each
+    way that gives 16 (words, pitch) classes: one word at pitch 4, 6, .. 14, two words at pitch 5,
+    7, .. 15, four words at pitch 9, 11, 13, 15 (tests/geometry_pools.py runs them all).
     """
     x_max = max(int(p["x_size"]) for p in puzzles)
     y_max = max(int(p["y_size"]) for p in puzzles)

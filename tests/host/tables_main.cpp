@@ -302,6 +302,7 @@ void check_puzzles(const Pool& p, const HostPuzzleTables& h) {
     for (size_t q = 0; q < P; ++q)
         if (s.X(q) * pitch > 57) ring = false;
     CHECK(h.ring_ok == ring, "ring_ok");
+    if (p.meta.count("expect_ring_ok")) CHECK(ring == (bool)p.get("expect_ring_ok", 0), "ring_ok %d: the pool reaches the branch the test means", (int)ring);
 }
 
 void check_hash(const Pool& p, const HostPuzzleTables& h) {
