@@ -28,6 +28,7 @@ import pytest
 from long_pools import column_snake, row_snake, square_pool, walk
 from oracle import COracle, OraclePool, _Env
 from record_path import decode, encode
+from small_shapes import base_families as _families   # the dispatch conditions of rollout_impl, restated once
 from sparc_gym_amd import _lib
 from sparc_gym_amd.puzzles import pack_table
 from sparc_gym_amd.search import rand_pick
@@ -128,25 +129,6 @@ def _script(name, n, align):
     acts[:len(script), 0::2] = np.asarray(script, np.uint8)[:, None]
     assert {33, 65, 129, P["points"] - 1} & set(range(P["points"])) <= {c[1] for c in cuts.values()}
     return acts, bounds, cuts
-
-
-def _families(table, n, T):
-    """The kernels one sparc_rollout_device call of T steps runs on n envs with 16-B aligned
-    buffers: the dispatch conditions of rollout_impl (sparc_kernels.hip), restated."""
-    tiled = n % 16 == 0
-    if table.words == 1:
-        # split1_pitch_ok and the 8-B trie records (every trie below 2^15 nodes)
-        split = tiled and n % 256 == 0 and T >= 16 and 3 <= table.pitch <= 9 and int(table.info[:, 3].max()) <= 0x7FFF
-        generic = "k_rollout1"
-    else:
-        # split_w of build_puzzle_tables: pitch <= 15, small tries, and the LDS layout fits, which
-        # tests/test_tables_host.py asserts for the gap-free 9x9 and 15x15 tables
-        split = (tiled and n % 256 == 0 and T >= 16 and table.pitch <= 15
-                 and int(table.info[:, 3].max()) <= 0x7FFF)
-        generic = "k_rollout"
-    if not split:
-        return {generic}
-    return {"k_rollout1s" if table.words == 1 else "k_rolloutWs"} | ({generic} if T % 16 else set())
 
 
 FAMILY = {"k_step": (64, 1), "k_rollout1s": (256, 16), "k_rollout1": (300, 1), "k_rolloutWs": (512, 16),
