@@ -456,6 +456,90 @@ int sparc_playout_host(void *ctx, const sparc_snapshot_info *info, const void *r
                        int32_t K, int32_t L, uint64_t seed, uint64_t id0, uint32_t flags,
                        const sparc_playout_out *out);
 
+/* ---- replay of given action sequences: scoring proposed paths, re-checking solutions ------------
+ * The deterministic counterpart of sparc_playout_device: M sequences (1 <= M < 2^31) of actions that
+ * the CALLER supplies, at most L each (0 <= L <= 65535), played in one launch and without touching
+ * an env: as with sparc_expand_device the context supplies its puzzle table, words, pitch,
+ * traceback, max_steps and autoreset mode only, its env state is neither read nor written, and
+ * sparc_load_puzzles is enough (no reset needed).
+ * Start of sequence j, exactly one of the two non-NULL (SPARC_E_INVALID otherwise):
+ *  d_records  [M] records: sequence j starts from record j, checked on the device with the
+ *             conditions of sparc_restore_device before anything is indexed with it
+ *  d_puzzle   [M] uint32: sequence j starts from the reset state of puzzle d_puzzle[j] (reset(),
+ *             SPaRC_Gym.py:1057-1108: what sparc_reset_device gives an env on that puzzle: step 0,
+ *             path length 1, not pending), checked < num_puzzles on the device.  info then still
+ *             describes the records WRITTEN.
+ * Actions: d_actions [L][M] uint8, step-major (the layout of sparc_playout_device's trace);
+ * d_len [M] uint32 (NULL: every sequence has L actions) is the number of actions of sequence j, a
+ * value above L is clamped to L.  There is no sentinel value: 255, like every value >= 4, is an
+ * illegal action and is stepped as one.
+ * With flags = 0 sequence j is byte for byte what sparc_restore_device of its start state, d_len[j]
+ * calls of sparc_step_device (step, SPaRC_Gym.py:1111-1238) with those actions, and
+ * sparc_snapshot_device give under the context's max_steps AND autoreset mode.  Nothing is
+ * special-cased, as in sparc_expand_device: an illegal action gives the no-move state with
+ * step + 1; under SPARC_AUTORESET_NONE a step after the end steps past it as the reference does;
+ * under SPARC_AUTORESET_NEXT_STEP a step after the end loads the next puzzle (flag bit 6).
+ *   SPARC_REPLAY_STOP_DONE     the sequence ends with the step that terminates or truncates; a start
+ *                              state whose last step ended its episode takes no step
+ *   SPARC_REPLAY_STOP_ILLEGAL  before each step, an action that is not in the state's legal mask
+ *                              (_get_legal_actions, 1024-1051; values >= 4 never are) ends the
+ *                              sequence there, and that action is NOT taken
+ * Any other flag bit is SPARC_E_INVALID.  End reason of a sequence:
+ *   SPARC_REPLAY_END_INVALID    0  the start fails its check: every output of the sequence is 0
+ *                                  (bad included), its records are zeroed, sparc_sync reports the
+ *                                  error, the other sequences are unaffected
+ *   SPARC_REPLAY_END_TERMINATED 1  stopped by STOP_DONE at a terminating step
+ *   SPARC_REPLAY_END_TRUNCATED  2  stopped by STOP_DONE at a truncating step
+ *   SPARC_REPLAY_END_EXHAUSTED  3  all d_len[j] actions were taken
+ *   SPARC_REPLAY_END_ILLEGAL    4  stopped by STOP_ILLEGAL
+ *   SPARC_REPLAY_END_PENDING    5  STOP_DONE, and the start was already done: no step
+ * Outputs (each may be NULL, at least one must not be):
+ *  code, flags [M] int8 / uint8: the last step's reward code and flag byte as sparc_step_device
+ *              writes them; 0 if no step was taken
+ *  steps       [M] uint16: steps taken
+ *  end         [M] uint8: the end reason
+ *  ret         [M] int32: the sum of the reward codes of the steps taken
+ *  bad         [M] uint16: the index of the action STOP_ILLEGAL refused; 0xFFFF if none
+ *  step_code, step_flags [L][M] int8 / uint8, step-major: the code and the flag byte of step t (the
+ *              legal actions of the NEW state in bits 2-5); 0 at and after the sequence's end
+ *  final_rec   [M] records (16-B aligned): the state the sequence ended in; with no step taken the
+ *              start record in canonical stored form (with d_puzzle and L = 0: the root records of
+ *              any puzzles, from a context that was never reset)
+ *  states      [L][M] records (16-B aligned), row t * M + j: the record after step t of sequence
+ *              j, zeroed at and after its end: the input of sparc_rules_records_device for the
+ *              per-step info['rule_status'] of a whole trace
+ * L = 0: d_actions, step_code, step_flags and states must be NULL; the call only makes the start
+ * records.  info must match the context as for a restore (SPARC_E_INVALID naming the field);
+ * d_records 16-B aligned.  Device pointers, asynchronous on the context's stream. */
+#define SPARC_REPLAY_STOP_DONE 1u
+#define SPARC_REPLAY_STOP_ILLEGAL 2u
+#define SPARC_REPLAY_END_INVALID 0
+#define SPARC_REPLAY_END_TERMINATED 1
+#define SPARC_REPLAY_END_TRUNCATED 2
+#define SPARC_REPLAY_END_EXHAUSTED 3
+#define SPARC_REPLAY_END_ILLEGAL 4
+#define SPARC_REPLAY_END_PENDING 5
+typedef struct {
+    int8_t *code;
+    uint8_t *flags;
+    uint16_t *steps;
+    uint8_t *end;
+    int32_t *ret;
+    uint16_t *bad;
+    int8_t *step_code;
+    uint8_t *step_flags;
+    void *final_rec;
+    void *states;
+} sparc_replay_out;
+int sparc_replay_device(void *ctx, const sparc_snapshot_info *info, const void *d_records,
+                        const uint32_t *d_puzzle, int64_t M, int32_t L, const uint8_t *d_actions,
+                        const uint32_t *d_len, uint32_t flags, const sparc_replay_out *out);
+/* the host-pointer form (every array and every member of out on the host, no alignment
+ * requirement): staged through the context's stream, returns after the data have moved */
+int sparc_replay_host(void *ctx, const sparc_snapshot_info *info, const void *records,
+                      const uint32_t *puzzle, int64_t M, int32_t L, const uint8_t *actions,
+                      const uint32_t *len, uint32_t flags, const sparc_replay_out *out);
+
 /* ---- rule audit: info['rule_status'] (_validate_rules, SPaRC_Gym.py:941-950) ----------------
  * Rule table, packed by sparc_gym_amd/puzzles.py:pack_rules from the processed puzzles, on the
  * step table's geometry (bit x*pitch + y, `words` u64 per board).

@@ -11,6 +11,7 @@
 //   k_snapshot / k_restore  the state as per-env records and back  (sparc_snapshot.hpp)
 //   k_rules_rec  rule audit of state records, without an env      (sparc_rules_rec.hpp)
 //   k_playout  K legal-move playouts of each state record, without an env (sparc_playout.hpp)
+//   k_replay   given action sequences played from records or puzzle roots, without an env (sparc_replay.hpp)
 //   k_dfs      depth-first subtree search of state records with rule verdicts (sparc_dfs.hpp)
 // No MFMA: this is integer / bitboard work, bound by latency and HBM.
 #include <hip/hip_runtime.h>
@@ -35,6 +36,7 @@
 #include "sparc_snapshot.hpp"
 #include "sparc_expand.hpp"
 #include "sparc_playout.hpp"
+#include "sparc_replay.hpp"
 #include "sparc_rules_rec.hpp"
 #include "sparc_dfs.hpp"
 #include "sparc_devbuf.hpp"
@@ -2043,6 +2045,8 @@ struct Ctx {
     // sparc_playout_host (sparc_playout.hpp): the per-playout outputs and the trace, the stats
     DevBuf<uint8_t> po_out;
     DevBuf<int32_t> po_stats;
+    // (sparc_replay_host shares these: fk_idx takes puzzle | len, ex_child the final | per-step records,
+    // po_out the per-sequence outputs, the actions and the per-step codes and flags)
     // sparc_dfs_host (sparc_dfs.hpp): cursor | first_sat records, the undecided records, and
     // counts [8M] | und_count | state [M] | und_root [cap] | status [M]
     DevBuf<uint8_t> df_rec, df_und;
@@ -2323,7 +2327,8 @@ int sparc_sync(void* ctx) {
         if (e & kErrJoin) return fail(c, SPARC_E_STATE, "rule rollout: an audit wave pair did not join (outputs unreliable)");
         if (e & kErrSnapshot)
             return fail(c, SPARC_E_INVALID,
-                        "snapshot / restore / fork / expand / playout / records audit: index or record out of range (those "
+                        "snapshot / restore / fork / expand / playout / replay / records audit: index or record out of range "
+                        "(those "
                         "envs unchanged, the children of those parents zeroed, the bits of those records 0)");
         return fail(c, SPARC_E_INVALID, "device-side puzzle index out of range in a reset");
     }
@@ -3678,6 +3683,117 @@ int sparc_playout_host(void* ctx, const sparc_snapshot_info* info, const void* r
         HIPCHK(c, hipMemcpyAsync(out->final_rec, d.final_rec, (size_t)info->record_bytes * mk, hipMemcpyDeviceToHost,
                                  c->stream));
     if (out->stats) HIPCHK(c, hipMemcpyAsync(out->stats, d.stats, 64 * m, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
+}
+
+// ---- replay of given action sequences (sparc_replay.hpp): reads the context's tables only
+static int check_replay_args(Ctx* c, const sparc_snapshot_info* info, const void* records, const uint32_t* puzzle,
+                             int64_t M, int32_t L, const uint8_t* actions, const uint32_t* len, uint32_t flags,
+                             const sparc_replay_out* out, bool device) {
+    int rc = check_snapshot_info(c, info);
+    if (rc) return rc;
+    if ((records != nullptr) == (puzzle != nullptr))
+        return fail(c, SPARC_E_INVALID, "exactly one of records and puzzle must be given");
+    if (!out) return fail(c, SPARC_E_INVALID, "null out");
+    if (M < 1 || M > 0x7FFFFFFFll) return fail(c, SPARC_E_INVALID, "M must be in 1..2^31-1");
+    if (L < 0 || L > 65535) return fail(c, SPARC_E_INVALID, "L must be in 0..65535");
+    if (flags & ~(SPARC_REPLAY_STOP_DONE | SPARC_REPLAY_STOP_ILLEGAL))
+        return fail(c, SPARC_E_INVALID, "unknown bits in flags");
+    if (L == 0 && (actions || out->step_code || out->step_flags || out->states))
+        return fail(c, SPARC_E_INVALID, "L = 0: actions, out->step_code, out->step_flags and out->states must be NULL");
+    if (L > 0 && !actions) return fail(c, SPARC_E_INVALID, "null actions");
+    if (!out->code && !out->flags && !out->steps && !out->end && !out->ret && !out->bad && !out->step_code &&
+        !out->step_flags && !out->final_rec && !out->states)
+        return fail(c, SPARC_E_INVALID, "out: at least one output is needed");
+    if (device) {
+        if ((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(out->final_rec) |
+             reinterpret_cast<uintptr_t>(out->states)) & 15u)
+            return fail(c, SPARC_E_INVALID, "records, out->final_rec and out->states must be 16-B aligned");
+        if (((reinterpret_cast<uintptr_t>(out->steps) | reinterpret_cast<uintptr_t>(out->bad)) & 1u) ||
+            ((reinterpret_cast<uintptr_t>(out->ret) | reinterpret_cast<uintptr_t>(puzzle) |
+              reinterpret_cast<uintptr_t>(len)) & 3u))
+            return fail(c, SPARC_E_INVALID, "puzzle, len, out->steps, out->bad and out->ret must be aligned to their type");
+    }
+    return SPARC_OK;
+}
+
+int sparc_replay_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, const uint32_t* d_puzzle,
+                        int64_t M, int32_t L, const uint8_t* d_actions, const uint32_t* d_len, uint32_t flags,
+                        const sparc_replay_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_replay_args(c, info, d_records, d_puzzle, M, L, d_actions, d_len, flags, out, true))) return rc;
+    const Params p = make_params(c);
+    const ReplayOut o{out->code, out->flags, out->steps,      out->end,
+                      out->ret,  out->bad,   out->step_code,  out->step_flags,
+                      static_cast<uint4*>(out->final_rec),    static_cast<uint4*>(out->states)};
+    const uint4* rec = static_cast<const uint4*>(d_records);
+    const uint32_t m = (uint32_t)M;
+    const dim3 gr((unsigned)(((uint64_t)M + kSnapBlock - 1) / kSnapBlock));
+    dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
+        constexpr int Wv = decltype(w)::value;
+        constexpr bool Tv = decltype(tb)::value;
+        if (out->states)
+            k_replay<Wv, Tv, true><<<gr, kSnapBlock, 0, c->stream>>>(p, rec, d_puzzle, m, (uint32_t)L, d_actions, d_len,
+                                                                     flags, o);
+        else
+            k_replay<Wv, Tv, false><<<gr, kSnapBlock, 0, c->stream>>>(p, rec, d_puzzle, m, (uint32_t)L, d_actions, d_len,
+                                                                      flags, o);
+    });
+    return launch_check(c);
+}
+
+int sparc_replay_host(void* ctx, const sparc_snapshot_info* info, const void* records, const uint32_t* puzzle, int64_t M,
+                      int32_t L, const uint8_t* actions, const uint32_t* len, uint32_t flags,
+                      const sparc_replay_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_replay_args(c, info, records, puzzle, M, L, actions, len, flags, out, false))) return rc;
+    const size_t m = (size_t)M, lm = (size_t)L * m, rb = (size_t)info->record_bytes;
+    // one scratch: ret [m] int32 | steps, bad [m] uint16 | code, flags, end [m] | actions, step_code, step_flags [L][m]
+    const size_t o_ret = 0, o_steps = 4 * m, o_bad = 6 * m, o_code = 8 * m, o_flags = 9 * m, o_end = 10 * m,
+                 o_act = 11 * m, o_scode = o_act + lm, o_sflags = o_scode + lm, total = o_sflags + lm;
+    HIPCHK(c, c->po_out.reserve(total));
+    HIPCHK(c, c->fk_idx.reserve(2 * m));
+    if (records) {
+        HIPCHK(c, c->fk_rec.reserve(rb * m));
+        HIPCHK(c, hipMemcpyAsync(c->fk_rec.get(), records, rb * m, hipMemcpyHostToDevice, c->stream));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(c->fk_idx.get(), puzzle, 4 * m, hipMemcpyHostToDevice, c->stream));
+    }
+    if (len) HIPCHK(c, hipMemcpyAsync(c->fk_idx.get() + m, len, 4 * m, hipMemcpyHostToDevice, c->stream));
+    // final [m] records, then states [L][m] records
+    if (out->final_rec || out->states) HIPCHK(c, c->ex_child.reserve(rb * (m + (out->states ? lm : 0))));
+    uint8_t* o = c->po_out.get();
+    if (L > 0) HIPCHK(c, hipMemcpyAsync(o + o_act, actions, lm, hipMemcpyHostToDevice, c->stream));
+    sparc_replay_out d{};
+    d.code = out->code ? reinterpret_cast<int8_t*>(o + o_code) : nullptr;
+    d.flags = out->flags ? o + o_flags : nullptr;
+    d.steps = out->steps ? reinterpret_cast<uint16_t*>(o + o_steps) : nullptr;
+    d.end = out->end ? o + o_end : nullptr;
+    d.ret = out->ret ? reinterpret_cast<int32_t*>(o + o_ret) : nullptr;
+    d.bad = out->bad ? reinterpret_cast<uint16_t*>(o + o_bad) : nullptr;
+    d.step_code = out->step_code ? reinterpret_cast<int8_t*>(o + o_scode) : nullptr;
+    d.step_flags = out->step_flags ? o + o_sflags : nullptr;
+    d.final_rec = out->final_rec ? c->ex_child.get() : nullptr;
+    d.states = out->states ? c->ex_child.get() + rb * m : nullptr;
+    rc = sparc_replay_device(c, info, records ? c->fk_rec.get() : nullptr, records ? nullptr : c->fk_idx.get(), M, L,
+                             L > 0 ? o + o_act : nullptr, len ? c->fk_idx.get() + m : nullptr, flags, &d);
+    if (rc) return rc;
+    if (out->code) HIPCHK(c, hipMemcpyAsync(out->code, d.code, m, hipMemcpyDeviceToHost, c->stream));
+    if (out->flags) HIPCHK(c, hipMemcpyAsync(out->flags, d.flags, m, hipMemcpyDeviceToHost, c->stream));
+    if (out->steps) HIPCHK(c, hipMemcpyAsync(out->steps, d.steps, 2 * m, hipMemcpyDeviceToHost, c->stream));
+    if (out->end) HIPCHK(c, hipMemcpyAsync(out->end, d.end, m, hipMemcpyDeviceToHost, c->stream));
+    if (out->ret) HIPCHK(c, hipMemcpyAsync(out->ret, d.ret, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    if (out->bad) HIPCHK(c, hipMemcpyAsync(out->bad, d.bad, 2 * m, hipMemcpyDeviceToHost, c->stream));
+    if (out->step_code) HIPCHK(c, hipMemcpyAsync(out->step_code, d.step_code, lm, hipMemcpyDeviceToHost, c->stream));
+    if (out->step_flags) HIPCHK(c, hipMemcpyAsync(out->step_flags, d.step_flags, lm, hipMemcpyDeviceToHost, c->stream));
+    if (out->final_rec) HIPCHK(c, hipMemcpyAsync(out->final_rec, d.final_rec, rb * m, hipMemcpyDeviceToHost, c->stream));
+    if (out->states) HIPCHK(c, hipMemcpyAsync(out->states, d.states, rb * lm, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 

@@ -74,6 +74,18 @@ class SparcPlayoutOut(ctypes.Structure):
                                         "stats")]
 
 
+REPLAY_STOP_DONE, REPLAY_STOP_ILLEGAL = 1, 2   # SPARC_REPLAY_STOP_*
+# SPARC_REPLAY_END_*: why a replayed sequence ended
+(REPLAY_END_INVALID, REPLAY_END_TERMINATED, REPLAY_END_TRUNCATED, REPLAY_END_EXHAUSTED, REPLAY_END_ILLEGAL,
+ REPLAY_END_PENDING) = range(6)
+
+
+class SparcReplayOut(ctypes.Structure):
+    """sparc_replay_out: the ten outputs of sparc_replay_device / _host, each may be NULL."""
+    _fields_ = [(k, c_void_p) for k in ("code", "flags", "steps", "end", "ret", "bad", "step_code", "step_flags",
+                                        "final_rec", "states")]
+
+
 # SPARC_DFS_*: the status of a record's walk after sparc_dfs_device
 DFS_INVALID, DFS_COMPLETE, DFS_BUDGET, DFS_PENDING, DFS_OVERFLOW = range(5)
 # the columns of its counters
@@ -139,6 +151,10 @@ _SIGS = {
                               c_uint64, c_uint64, ctypes.c_uint32, ctypes.POINTER(SparcPlayoutOut)], c_int32),
     "sparc_playout_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_int32, c_int32,
                             c_uint64, c_uint64, ctypes.c_uint32, ctypes.POINTER(SparcPlayoutOut)], c_int32),
+    "sparc_replay_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, c_void_p, ctypes.c_int64, c_int32,
+                             c_void_p, c_void_p, ctypes.c_uint32, ctypes.POINTER(SparcReplayOut)], c_int32),
+    "sparc_replay_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, c_void_p, ctypes.c_int64, c_int32,
+                           c_void_p, c_void_p, ctypes.c_uint32, ctypes.POINTER(SparcReplayOut)], c_int32),
     "sparc_dfs_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, ctypes.c_uint32,
                           c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
     "sparc_dfs_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, ctypes.c_uint32,

@@ -363,6 +363,77 @@ class SparcCore:
                                                 ctypes.byref(o)))
         return out
 
+    # ---------------------------------------------------------------- replay of given action sequences
+    @staticmethod
+    def _check_replay(records, puzzle, M, L, actions, flags, outputs, per_step):
+        """The argument rules of sparc_replay_device that need no device (ValueError)."""
+        if (records is None) == (puzzle is None):
+            raise ValueError("exactly one of records and puzzle must be given")
+        if not 1 <= M < 2**31:
+            raise ValueError("M must be in 1..2^31-1")
+        if not 0 <= L <= 65535:
+            raise ValueError("L must be in 0..65535")
+        if flags & ~(_lib.REPLAY_STOP_DONE | _lib.REPLAY_STOP_ILLEGAL):
+            raise ValueError("unknown bits in flags")
+        if L == 0 and (actions is not None or any(x is not None for x in per_step)):
+            raise ValueError("L = 0: actions, step_code, step_flags and states must be None")
+        if L > 0 and actions is None:
+            raise ValueError("actions are needed for L > 0")
+        if all(x is None for x in outputs):
+            raise ValueError("out: at least one output is needed")
+
+    def replay_device(self, info, d_records, d_puzzle, M, L, d_actions, d_len=None, flags=0, d_code=None,
+                      d_flags=None, d_steps=None, d_end=None, d_return=None, d_bad=None, d_step_code=None,
+                      d_step_flags=None, d_final=None, d_states=None):
+        """sparc_replay_device: M sequences of at most L given actions ([L][M] uint8, lengths d_len [M]
+        uint32 or None), each from record j of d_records or from the reset state of puzzle
+        d_puzzle[j] (exactly one of the two); outputs [M] (step_code, step_flags [L][M]; final [M]
+        records, states [L][M] records), each may be None; reads the context's tables only
+        (asynchronous)."""
+        M, L, flags = int(M), int(L), int(flags)
+        per_step = (d_step_code, d_step_flags, d_states)
+        outs = (d_code, d_flags, d_steps, d_end, d_return, d_bad, d_final) + per_step
+        self._check_replay(d_records, d_puzzle, M, L, d_actions, flags, outs, per_step)
+        out = _lib.SparcReplayOut(d_code, d_flags, d_steps, d_end, d_return, d_bad, d_step_code, d_step_flags, d_final,
+                                  d_states)
+        self._check(self.lib.sparc_replay_device(self.ctx, ctypes.byref(info), d_records, d_puzzle, M, L, d_actions,
+                                                 d_len, flags, ctypes.byref(out)))
+
+    def replay_host(self, info, actions, records=None, puzzle=None, lengths=None, flags=0, per_step=False,
+                    final=True, states=False):
+        """Replay host action lists ``actions`` [L, M] uint8 from host records [M, record_bytes] or
+        from the reset states of ``puzzle`` [M]: a dict of host arrays ``code`` int8, ``flags`` uint8,
+        ``steps`` uint16, ``end`` uint8, ``ret`` int32, ``bad`` uint16 (each [M]), optionally
+        ``step_code`` / ``step_flags`` [L, M], ``final`` [M, record_bytes] and ``states``
+        [L * M, record_bytes] uint8 (synchronous)."""
+        act = np.ascontiguousarray(actions, np.uint8)
+        if act.ndim != 2:
+            raise ValueError("actions must be [L, M] uint8")
+        L, M = act.shape
+        rec = None if records is None else np.ascontiguousarray(records, np.uint8)
+        if rec is not None and (rec.ndim != 2 or rec.shape != (M, info.record_bytes)):
+            raise ValueError(f"records must be [{M}, {info.record_bytes}] uint8")
+        pz = None if puzzle is None else np.ascontiguousarray(puzzle, np.uint32)
+        ln = None if lengths is None else np.ascontiguousarray(lengths, np.uint32)
+        for a, what in ((pz, "puzzle"), (ln, "lengths")):
+            if a is not None and a.shape != (M,):
+                raise ValueError(f"{what} must have shape ({M},)")
+        out = {"code": np.empty(M, np.int8), "flags": np.empty(M, np.uint8), "steps": np.empty(M, np.uint16),
+               "end": np.empty(M, np.uint8), "ret": np.empty(M, np.int32), "bad": np.empty(M, np.uint16)}
+        if per_step and L:
+            out["step_code"], out["step_flags"] = np.empty((L, M), np.int8), np.empty((L, M), np.uint8)
+        if final:
+            out["final"] = np.empty((M, info.record_bytes), np.uint8)
+        if states and L:
+            out["states"] = np.empty((L * M, info.record_bytes), np.uint8)
+        per = tuple(out.get(k) for k in ("step_code", "step_flags", "states"))
+        self._check_replay(rec, pz, M, L, act if L else None, int(flags), tuple(out.values()), per)
+        o = _lib.SparcReplayOut(*(_ptr(out.get(k)) for k in ("code", "flags", "steps", "end", "ret", "bad",
+                                                              "step_code", "step_flags", "final", "states")))
+        self._check(self.lib.sparc_replay_host(self.ctx, ctypes.byref(info), _ptr(rec), _ptr(pz), M, L,
+                                               _ptr(act) if L else None, _ptr(ln), int(flags), ctypes.byref(o)))
+        return out
+
     # ---------------------------------------------------------------- depth-first subtree search of records
     def dfs_device(self, info, d_records, M, budget, d_state, d_status, d_counts, d_cursor, d_first=None,
                    d_und_rec=None, d_und_root=None, d_und_count=None, und_cap=0):

@@ -187,6 +187,84 @@ def monte_carlo(vec, snap, playouts, horizon, seed=0, forward_only=None):
             "solution": solution}
 
 
+ILLEGAL_ACTION = 255   # an action value no state accepts (any value above 3 is illegal)
+
+
+def actions_from_points(start, points):
+    """A path given as points, the dataset's solution format (a list of ``(x, y)`` or of
+    ``{'x': .., 'y': ..}`` dicts, the first one the puzzle's start), as the actions that walk it:
+    0 right (x + 1), 1 up (y - 1), 2 left (x - 1), 3 down (y + 1), the step's order in
+    SPaRC_Gym.py:1131-1188.  A step that is not a unit move (a diagonal, a jump, a repeated point)
+    becomes action 255, which no state accepts.  Pure numpy.
+
+    Returns ``(actions, starts_ok)``: ``actions`` uint8 [len(points) - 1] (empty for fewer than two
+    points) and whether the first point is ``start`` (True for an empty list: nothing contradicts
+    it)."""
+    pts = np.asarray([(p["x"], p["y"]) if isinstance(p, dict) else (p[0], p[1]) for p in points], np.int64)
+    pts = pts.reshape(-1, 2)
+    starts_ok = len(pts) == 0 or (int(pts[0, 0]), int(pts[0, 1])) == (int(start[0]), int(start[1]))
+    if len(pts) < 2:
+        return np.zeros(0, np.uint8), starts_ok
+    dx, dy = np.diff(pts[:, 0]), np.diff(pts[:, 1])
+    acts = np.full(len(pts) - 1, ILLEGAL_ACTION, np.uint8)
+    for a, (mx, my) in enumerate(((1, 0), (0, -1), (-1, 0), (0, 1))):
+        acts[(dx == mx) & (dy == my)] = a
+    return acts, starts_ok
+
+
+def score_paths(vec, puzzle_indices, paths, as_points=False):
+    """The puzzle's verdict on proposed paths, any number of them on any puzzles: path ``k`` is
+    walked from the reset state of puzzle ``puzzle_indices[k]`` in ONE ``vec.replay`` launch from
+    ``vec.roots`` with both stop flags (it ends at its first illegal action, which is not taken, or
+    with the step that terminates or truncates), and the end states that terminated are judged by
+    ``vec.audit_records``.  ``paths``: per path its actions, or with ``as_points`` its points
+    (``actions_from_points``; a path whose first point is not the puzzle's start is replaced by
+    the single action 255, so it is refused at index 0 without a step).  Touches no env and does
+    not depend on ``vec.num_envs``.
+
+    Returns a dict of numpy arrays [K]: ``end`` (``_lib.REPLAY_END_*``), ``steps``, ``first_bad``
+    (the index of the refused action, -1 if none), ``reached`` (ended terminated, on the target,
+    with every action consumed), ``listed`` (the last step's reward code was +100: the path is in
+    the puzzle's solution list), ``bits`` int64 (the rule bits of the end state, 0 where it was not
+    audited) and ``satisfied`` (``bits & RULE_ALL``)."""
+    from . import _lib
+    q = np.asarray(puzzle_indices, np.int64)
+    K = len(paths)
+    if q.ndim != 1 or len(q) != K or K < 1:
+        raise ValueError("puzzle_indices and paths must hold the same number (at least one) of entries")
+    seqs = []
+    for k, path in enumerate(paths):
+        if as_points:
+            acts, ok = actions_from_points(vec.puzzles[int(q[k])]["start_location"], path)
+            if not ok:
+                acts = np.array([ILLEGAL_ACTION], np.uint8)
+        else:
+            acts = np.asarray(path, np.int64).reshape(-1)
+            if ((acts < 0) | (acts > 255)).any():
+                raise ValueError(f"path {k}: actions must be in 0..255")
+            acts = acts.astype(np.uint8)
+        seqs.append(acts)
+    lengths = np.array([len(s) for s in seqs], np.int64)
+    L = max(int(lengths.max()), 1)
+    actions = np.full((L, K), ILLEGAL_ACTION, np.uint8)
+    for k, s in enumerate(seqs):
+        actions[:len(s), k] = s
+    out = vec.replay(vec.roots(q), actions, lengths=lengths, stop_done=True, stop_illegal=True)
+    end = out["end"].cpu().numpy().astype(np.int64)
+    steps = out["steps"].cpu().numpy().astype(np.int64)
+    bad = out["bad"].cpu().numpy().astype(np.int64)
+    code = out["reward_code"].cpu().numpy().astype(np.int64)
+    term = end == _lib.REPLAY_END_TERMINATED
+    bits = np.zeros(K, np.int64)
+    if term.any():
+        rows = np.nonzero(term)[0]
+        got = vec.audit_records(out["final"].select(rows))["bits"].to(torch.int64) & 0xFFFF
+        bits[rows] = got.cpu().numpy()
+    return {"end": end, "steps": steps, "first_bad": np.where(bad == 0xFFFF, -1, bad),
+            "reached": term & (steps == lengths), "listed": code == 100, "bits": bits,
+            "satisfied": (bits & RULE_ALL) != 0}
+
+
 def solve_dfs(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, undecided=65536):
     """Every self-avoiding path from the start of each of ``puzzle_indices`` (one root per entry:
     that puzzle's reset state, all roots at once) counted with the puzzle's own verdict, as

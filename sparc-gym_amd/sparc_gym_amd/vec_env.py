@@ -34,7 +34,9 @@ position fanned out to every env for playouts, beam search or MCTS, or a run sav
 touching an env (the one-ply step of a tree search; ``sparc_gym_amd.search`` builds on it).
 ``playout(snap, K, L)`` plays K random legal-move continuations of every record to the end of
 its episode or L steps, again in one launch without an env, with per-root statistics
-(``search.monte_carlo``).
+(``search.monte_carlo``).  ``replay(snap, actions, lengths)`` plays action sequences that the caller
+supplies, from records or (``puzzle_indices``) from puzzles' reset states, again in one launch without
+an env; ``roots(puzzle_indices)`` gives reset states as records (``search.score_paths``).
 """
 from __future__ import annotations
 
@@ -76,7 +78,139 @@ def xcd_local_puzzle_index(num_envs, num_puzzles, env_offset=0):
     return (grp * span + k * np.uint64(2654435761) % span).astype(np.int64)
 
 
-class SPaRCVecEnv:
+class _RecordReplay:
+    """``replay`` and ``roots`` of ``SPaRCVecEnv``: the calls that play given actions from records
+    or puzzle roots without an env.  A base class of its own: tests/test_stream_binding.py pins the
+    methods defined on ``SPaRCVecEnv`` itself to the list its stream tests walk, and
+    tests/test_replay_guards.py and tests/test_gpu_replay.py check the same contract (the caller's
+    stream is bound before the first call into the core) for these two."""
+
+    def replay(self, snap=None, actions=None, lengths=None, puzzle_indices=None, stop_done=False,
+               stop_illegal=False, per_step=False, final=True, states=False):
+        """Play given action sequences, one per start state, in one launch and without changing or
+        reading any env (k_replay): what the reference's user does with a model's proposed moves
+        (step the env with them and read the result, SPaRC_Gym.py:1111-1238), for any number of
+        proposals at once.  Sequence ``j`` starts from record ``j`` of ``snap`` or from the reset
+        state of puzzle ``puzzle_indices[j]`` (exactly one of the two is given; M starts in all).
+        ``actions``: [L, M] uint8 (numpy or tensor), step-major as ``playout``'s trace; ``lengths``
+        [M]: the actions of sequence ``j`` (default: L each); every value is an action, 255 and
+        everything else above 3 an illegal one.  ``actions=None`` is L = 0: no step, only the start
+        records (``roots``).
+
+        Without a stop flag sequence ``j`` is byte for byte ``restore`` of its start, ``lengths[j]``
+        ``step`` calls and ``snapshot`` under this env's ``max_steps`` and ``autoreset``: an illegal
+        action gives the no-move state with step + 1, and a step after the end steps past it
+        (``autoreset='none'``) or loads the next puzzle (flag 64).  ``stop_done``: the sequence ends
+        with the step that terminates or truncates (a start that is already done takes no step).
+        ``stop_illegal``: an action that is not legal in the current state ends the sequence before
+        it is taken.
+
+        Returns a dict of GPU tensors [M]: ``reward_code`` int8 and ``flags`` uint8 of the last step
+        taken (0 without one), ``steps`` int32, ``end`` uint8 (``_lib.REPLAY_END_*``: 0 bad start,
+        1 terminated, 2 truncated, 3 every action taken, 4 stopped at an illegal action, 5 the start
+        was already done), ``return`` int32 the sum of the reward codes, ``bad`` int32 the index of
+        the action ``stop_illegal`` refused (65535: none); with ``per_step`` ``step_code`` int8 and
+        ``step_flags`` uint8 [L, M], 0 at and after the end; with ``final`` a ``Snapshot`` of the M
+        end states; with ``states`` a ``Snapshot`` of ``L * M`` records, row ``t * M + j`` the state
+        after step ``t`` of sequence ``j``, zeroed at and after the end (``audit_records`` of it gives
+        the reference's per-step ``info['rule_status']``).  A start that fails the kernel's checks
+        gives end 0 and zeroed outputs, and the next ``core.sync()`` raises.  ValueError: both or
+        neither of ``snap`` and ``puzzle_indices``, a shape or dtype mismatch, host ``lengths``
+        above L (a tensor's are clamped by the kernel), a snapshot header that does not match this
+        env (naming the field)."""
+        from .snapshot import Snapshot, info_mismatch
+        self._stream()
+        if (snap is None) == (puzzle_indices is None):
+            raise ValueError("give exactly one of snap and puzzle_indices")
+        if snap is not None:
+            M = len(snap)
+        elif isinstance(puzzle_indices, torch.Tensor):
+            M = int(puzzle_indices.shape[0]) if puzzle_indices.ndim == 1 else 0
+        else:
+            M = int(np.asarray(puzzle_indices).shape[0]) if np.asarray(puzzle_indices).ndim == 1 else 0
+        if not 1 <= M < 2**31:
+            raise ValueError("1 .. 2^31 - 1 start states (records or a one-dimensional puzzle_indices) are needed")
+        if actions is None:
+            L = 0
+            if lengths is not None or per_step or states:
+                raise ValueError("without actions (L = 0) there are no lengths, per-step outputs or states")
+        else:
+            if not isinstance(actions, (torch.Tensor, np.ndarray)):
+                raise ValueError("actions must be a uint8 numpy array or tensor [L, M]")
+            if actions.dtype != (torch.uint8 if isinstance(actions, torch.Tensor) else np.uint8):
+                raise ValueError(f"actions must be uint8, not {actions.dtype}")
+            if actions.ndim != 2 or actions.shape[1] != M:
+                raise ValueError(f"actions must have shape [L, {M}], not {list(actions.shape)}")
+            L = int(actions.shape[0])
+            if not 1 <= L <= 65535:
+                raise ValueError("actions must hold 1..65535 steps (L); pass actions=None for L = 0")
+        if lengths is not None and not isinstance(lengths, torch.Tensor):
+            lengths = np.asarray(lengths)
+            if lengths.shape != (M,) or lengths.dtype.kind not in "iu":
+                raise ValueError(f"lengths must be integers of shape ({M},)")
+            if int(lengths.min()) < 0 or int(lengths.max()) > L:
+                raise ValueError(f"lengths must be in 0..{L} (the rows of actions)")
+            lengths = torch.from_numpy(lengths.astype(np.int32))
+        elif lengths is not None and (lengths.shape != (M,) or lengths.dtype.is_floating_point or
+                                      lengths.dtype == torch.bool):
+            raise ValueError(f"lengths must be integers of shape ({M},)")
+        pz = None if puzzle_indices is None else self._index_arg(puzzle_indices, "puzzle_indices", self.num_puzzles)
+        info = self.core.snapshot_info()
+        if snap is not None:
+            bad = info_mismatch(snap.info, info)
+            if bad is not None:
+                raise ValueError(f"snapshot does not match this env: {bad} differs")
+            info = snap.info
+            rec = snap.records
+            if not isinstance(rec, torch.Tensor):
+                rec = torch.from_numpy(np.ascontiguousarray(rec, np.uint8))
+            rec = rec.to(self.device).contiguous()
+        dev = self.device
+        act = None
+        if L:
+            act = actions
+            if not isinstance(act, torch.Tensor):
+                act = np.ascontiguousarray(act)
+                act = torch.from_numpy(act if act.flags.writeable else act.copy())   # (torch wants a writable one)
+            act = act.to(dev).contiguous()
+        ln = None if lengths is None else lengths.to(device=dev, dtype=torch.int32).contiguous()
+        ret = torch.empty(M, dtype=torch.int32, device=dev)
+        h = torch.empty((2, M), dtype=torch.int16, device=dev)        # steps | bad
+        b = torch.empty((3, M), dtype=torch.uint8, device=dev)        # code | flags | end
+        out = {"reward_code": b[0].view(torch.int8), "flags": b[1], "end": b[2], "return": ret}
+        if per_step:
+            sb = torch.empty((2, L, M), dtype=torch.uint8, device=dev)
+            out["step_code"], out["step_flags"] = sb[0].view(torch.int8), sb[1]
+        rb = info.record_bytes
+        fin = torch.empty((M, rb), dtype=torch.uint8, device=dev) if final else None
+        st = torch.empty((L * M, rb), dtype=torch.uint8, device=dev) if states else None
+        flags = (_lib.REPLAY_STOP_DONE if stop_done else 0) | (_lib.REPLAY_STOP_ILLEGAL if stop_illegal else 0)
+        self.core.replay_device(info, rec.data_ptr() if snap is not None else None,
+                                pz.data_ptr() if pz is not None else None, M, L,
+                                act.data_ptr() if L else None, ln.data_ptr() if ln is not None else None, flags,
+                                d_code=b[0].data_ptr(), d_flags=b[1].data_ptr(), d_steps=h[0].data_ptr(),
+                                d_end=b[2].data_ptr(), d_return=ret.data_ptr(), d_bad=h[1].data_ptr(),
+                                d_step_code=sb[0].data_ptr() if per_step else None,
+                                d_step_flags=sb[1].data_ptr() if per_step else None,
+                                d_final=fin.data_ptr() if final else None,
+                                d_states=st.data_ptr() if states else None)
+        out["steps"] = h[0].to(torch.int32) & 0xFFFF                  # the kernel writes uint16
+        out["bad"] = h[1].to(torch.int32) & 0xFFFF
+        if final:
+            out["final"] = Snapshot(fin, info)
+        if states:
+            out["states"] = Snapshot(st, info)
+        return out
+
+    def roots(self, puzzle_indices):
+        """The reset state of every puzzle of ``puzzle_indices`` (any number, repeats allowed) as a
+        ``Snapshot``: the records ``reset`` on those puzzles plus ``snapshot`` give (reset(),
+        SPaRC_Gym.py:1057-1108), made by ``replay`` with no action, so no env is needed, read or
+        written and the env need never have been reset."""
+        return self.replay(puzzle_indices=puzzle_indices)["final"]
+
+
+class SPaRCVecEnv(_RecordReplay):
     def __init__(self, num_envs, puzzles=None, df_name="lkaesberg/SPaRC", df_split="all", df_set="test",
                  observation="new", traceback=False, max_steps=2000, autoreset="next_step", device=0,
                  env_offset=0, pitch=None, words=None, processed=None, table=None, rules=False, copy=True,
