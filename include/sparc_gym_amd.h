@@ -540,6 +540,70 @@ int sparc_replay_host(void *ctx, const sparc_snapshot_info *info, const void *re
                       const uint32_t *puzzle, int64_t M, int32_t L, const uint8_t *actions,
                       const uint32_t *len, uint32_t flags, const sparc_replay_out *out);
 
+/* ---- observation planes of records: a search frontier as a network's input ---------------------
+ * The 'visited' and 'agent_location' planes of obs['base'] (_get_obs, SPaRC_Gym.py:956-979) of M
+ * records (1 <= M < 2^31, independent of num_envs), with the puzzle index, the agent's location and
+ * the legal actions of each, in one launch and without touching an env: as with
+ * sparc_expand_device the context supplies its puzzle table, words, pitch and traceback mode only,
+ * its env state is neither read nor written, and sparc_load_puzzles is enough (no reset needed).
+ *  visited, agent  the planes of record j, [x_dim][y_dim] elements at element j * stride of each
+ *                  pointer: bit for bit (as elements of `elem`) what sparc_obs_pack_device writes for
+ *                  an env restored from record j by sparc_restore_device.  Cell (x, y) of visited is
+ *                  board bit x * pitch + y when y < pitch and the bit is below 64 * words, else 0;
+ *                  agent is 1 exactly at the record's (x, y).  A pending (finished) record is
+ *                  observed as it stands.
+ *  elem            the element type, SPARC_OBS_*: 1 is the integer 1 (I32, the reference's dtype,
+ *                  and U8) or the float 1.0 (F16 0x3C00, BF16 0x3F80, F32 0x3F800000); 0 is
+ *                  all-zero bits in every type
+ *  x_dim, y_dim    the plane's size: not below the table's largest x_size / y_size,
+ *                  x_dim * y_dim <= 256; cells outside a puzzle's lattice are 0
+ *  stride          elements between the planes of consecutive records; 0 means dense
+ *                  (x_dim * y_dim), otherwise stride >= x_dim * y_dim.  One stride with two base
+ *                  pointers aims the two planes at two channels of a caller's [M][C][x_dim][y_dim]
+ *                  tensor (stride = C * x_dim * y_dim); nothing outside the two planes of each
+ *                  record is written
+ *  puzzle          [M] uint32: the record's puzzle index
+ *  loc             [M][2] int32: the agent's (x, y)
+ *  legal           [M] uint8: the legal actions of the record's state in bits 0-3
+ *                  (_get_legal_actions, 1024-1051), exactly (flags >> 2) & 15 of
+ *                  sparc_restore_device's d_flags for that record, under the context's traceback mode
+ * Every output may be NULL, at least one must not be.  info must match the context as for
+ * sparc_expand_device (SPARC_E_INVALID naming the field).  SPARC_E_INVALID, naming the argument and
+ * before any launch, also for: an unknown elem; x_dim / y_dim below the table's maxima or
+ * x_dim * y_dim > 256; 0 < stride < x_dim * y_dim; M outside 1 .. 2^31 - 1; d_records NULL or not
+ * 16-B aligned; visited / agent not aligned to the element.  Whole 16-B stores are used where the
+ * planes allow them (dense: both arrays 16-B aligned; strided: every 16-B aligned piece of memory
+ * that lies inside a plane, whatever the stride and the alignment of the plane's start), element
+ * stores elsewhere: the result does not depend on it.
+ * Every record is checked on the device before anything is indexed with it, with the conditions of
+ * sparc_restore_device.  A record that fails gets two all-zero planes, puzzle 0xFFFFFFFF, loc
+ * (0, 0) and legal 0, and sparc_sync reports the error; every other record is unaffected.  Device
+ * pointers, asynchronous on the context's stream. */
+#define SPARC_OBS_I32 0
+#define SPARC_OBS_U8 1
+#define SPARC_OBS_F16 2
+#define SPARC_OBS_BF16 3
+#define SPARC_OBS_F32 4
+typedef struct {
+    void *visited;
+    void *agent;
+    int32_t elem;
+    int32_t x_dim;
+    int32_t y_dim;
+    int32_t reserved;   /* 0 */
+    int64_t stride;
+    uint32_t *puzzle;
+    int32_t *loc;
+    uint8_t *legal;
+} sparc_observe_out;
+int sparc_observe_records_device(void *ctx, const sparc_snapshot_info *info, const void *d_records, int64_t M,
+                                 const sparc_observe_out *out);
+/* the host-pointer form (records and every member of out on the host, no alignment requirement):
+ * staged through the context's stream, returns after the data have moved; with a stride only the
+ * planes themselves are written in the caller's arrays */
+int sparc_observe_records_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
+                               const sparc_observe_out *out);
+
 /* ---- rule audit: info['rule_status'] (_validate_rules, SPaRC_Gym.py:941-950) ----------------
  * Rule table, packed by sparc_gym_amd/puzzles.py:pack_rules from the processed puzzles, on the
  * step table's geometry (bit x*pitch + y, `words` u64 per board).

@@ -247,6 +247,11 @@ __device__ __forceinline__ void obs_stage(ObsWave<W>* ow, uint32_t lane, bool ha
 template <int W>
 __device__ __forceinline__ void obs_write(const ObsWave<W>* ow, const uint16_t* lut, uint32_t lane, uint32_t cnt,
                                           uint32_t XY, int32_t* __restrict__ vout, int32_t* __restrict__ aout);
+// ... for any element size and plane stride (below)
+template <int W, class E, bool STRIDED>
+__device__ __forceinline__ void obs_write_as(const ObsWave<W>* ow, const uint16_t* lut, uint32_t lane, uint32_t cnt,
+                                             uint32_t XY, E* __restrict__ vout, E* __restrict__ aout, uint32_t one,
+                                             size_t stride);
 
 // the wave's envs [0, cnt) -> planes at vout / aout (run starts, entry `base` of the whole
 // array, for the alignment test); every lane of the wave must call this (wave-uniform)
@@ -260,49 +265,133 @@ __device__ __forceinline__ void obs_emit(ObsWave<W>* ow, const uint16_t* lut, ui
     wave_lds_fence();
 }
 
-template <int W>
-__device__ __forceinline__ void obs_write(const ObsWave<W>* ow, const uint16_t* lut, uint32_t lane, uint32_t cnt,
-                                          uint32_t XY, int32_t* __restrict__ vout, int32_t* __restrict__ aout) {
-    const uint32_t total = cnt * XY;
-    // 16-B stores need both runs 16-B aligned (true whenever N * XY % 4 == 0)
-    const bool vec = (((reinterpret_cast<uintptr_t>(vout) | reinterpret_cast<uintptr_t>(aout)) & 15u) == 0);
-    uint32_t f = 4u * lane;                       // first entry of this lane's piece
-    uint32_t l = f / XY, c = f - l * XY;          // its env and cell
-    const uint32_t dl = 256u / XY, dc = 256u - dl * XY;   // a 64-piece stride in envs / cells
-    for (; f < total; f += 256u) {
-        uint32_t vv[4], aa[4];
-        uint32_t ll = l, cc = c;
+// The planes' element type is a launch argument of the record observation (sparc_observe.hpp): E
+// is the unsigned integer of the element's size (1, 2 or 4 bytes) and `one` the bit pattern of 1
+// in it (zero is all-zero bits in every type); the rollout kernels write int32 planes, E =
+// uint32_t with one = 1.  A 16-B piece holds 16 / sizeof(E) elements, element k at byte
+// k * sizeof(E).
+template <class E>
+__device__ __forceinline__ u32x4 obs_piece(const uint32_t (&v)[16 / sizeof(E)]) {
+    constexpr int kPer = 4 / sizeof(E);   // elements per 32-bit word
+    uint32_t d[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t b = lut[cc];
-            const uint32_t word = ow->vis[(b >> 5) & (2 * W - 1)][ll & 63u];
-            vv[k] = b == kObsNone ? 0u : (word >> (b & 31u)) & 1u;
-            aa[k] = b == ow->ab[ll & 63u] ? 1u : 0u;
-            ++cc;
-            if (cc == XY) {
-                cc = 0;
-                ++ll;
-            }
+    for (int k = 0; k < (int)(16 / sizeof(E)); ++k) d[k / kPer] |= v[k] << (8 * sizeof(E) * (k % kPer));
+    return u32x4{d[0], d[1], d[2], d[3]};
+}
+
+// visited and agent entry of cell cc of staged env ll, as `one` or 0
+template <int W>
+__device__ __forceinline__ void obs_cell(const ObsWave<W>* ow, const uint16_t* lut, uint32_t ll, uint32_t cc,
+                                         uint32_t one, uint32_t& v, uint32_t& a) {
+    const uint32_t b = lut[cc];
+    const uint32_t word = ow->vis[(b >> 5) & (2 * W - 1)][ll & 63u];
+    v = b == kObsNone ? 0u : (0u - ((word >> (b & 31u)) & 1u)) & one;
+    a = b == ow->ab[ll & 63u] ? one : 0u;
+}
+
+// One plane (visited, or AGENT) of the staged envs [0, cnt) with the plane of env l at element
+// l * stride (stride >= XY) of `out`: the planes of a wave are not one run, so the pieces are the
+// 16-B ALIGNED pieces of memory that each plane touches, whatever the alignment of its start (an
+// odd plane size, a channel of a larger tensor): a piece that lies inside the plane is one 16-B
+// store, the one or two that stick out at its ends are element stores of the cells inside, and
+// nothing is written between the planes.  A plane touches at most (XY + 2 * per-piece - 2) /
+// per-piece pieces; piece cp of env l starts at cell cp * per-piece - (the plane start's offset in
+// its first piece).
+template <int W, class E, bool AGENT>
+__device__ __forceinline__ void obs_write_plane(const ObsWave<W>* ow, const uint16_t* lut, uint32_t lane, uint32_t cnt,
+                                                uint32_t XY, E* __restrict__ out, uint32_t one, size_t stride) {
+    constexpr uint32_t kPer = 16u / sizeof(E);
+    const uint64_t e_base = reinterpret_cast<uintptr_t>(out) / sizeof(E);   // the first plane's start, in elements
+    const uint32_t ppp = (XY + 2u * kPer - 2u) / kPer, total = cnt * ppp;
+    uint32_t l = lane / ppp, cp = lane - l * ppp;         // this lane's env and piece of its plane
+    const uint32_t dl = 64u / ppp, dc = 64u - dl * ppp;   // a 64-piece stride in envs / pieces
+    for (uint32_t q = lane; q < total; q += 64u) {
+        const uint32_t a = (uint32_t)((e_base + (uint64_t)l * stride) & (kPer - 1u));
+        const int32_t c0 = (int32_t)(cp * kPer) - (int32_t)a;
+        uint32_t vv[kPer];
+#pragma unroll
+        for (uint32_t k = 0; k < kPer; ++k) {
+            const int32_t c = c0 + (int32_t)k;
+            uint32_t v = 0u, g = 0u;
+            if (c >= 0 && c < (int32_t)XY) obs_cell<W>(ow, lut, l, (uint32_t)c, one, v, g);
+            vv[k] = AGENT ? g : v;
         }
-        if (vec && f + 4u <= total) {
-            if (vout) __builtin_nontemporal_store(u32x4{vv[0], vv[1], vv[2], vv[3]}, reinterpret_cast<u32x4*>(vout + f));
-            if (aout) __builtin_nontemporal_store(u32x4{aa[0], aa[1], aa[2], aa[3]}, reinterpret_cast<u32x4*>(aout + f));
+        E* at = out + (size_t)l * stride;   // the plane; at + c0 is 16-B aligned
+        if (c0 >= 0 && c0 + (int32_t)kPer <= (int32_t)XY) {
+            __builtin_nontemporal_store(obs_piece<E>(vv), reinterpret_cast<u32x4*>(at + c0));
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (f + k < total) {
-                    if (vout) vout[f + k] = (int32_t)vv[k];
-                    if (aout) aout[f + k] = (int32_t)aa[k];
-                }
+            for (uint32_t k = 0; k < kPer; ++k) {
+                const int32_t c = c0 + (int32_t)k;
+                if (c >= 0 && c < (int32_t)XY) at[c] = (E)vv[k];
             }
         }
-        c += dc;
+        cp += dc;
         l += dl;
-        if (c >= XY) {
-            c -= XY;
+        if (cp >= ppp) {
+            cp -= ppp;
             ++l;
         }
     }
+}
+
+// STRIDED false: the planes of the wave's envs are one dense run of cnt * XY elements, cut into
+// 16-B pieces whichever env they belong to.  STRIDED true: obs_write_plane for each plane.
+template <int W, class E, bool STRIDED>
+__device__ __forceinline__ void obs_write_as(const ObsWave<W>* ow, const uint16_t* lut, uint32_t lane, uint32_t cnt,
+                                             uint32_t XY, E* __restrict__ vout, E* __restrict__ aout, uint32_t one,
+                                             size_t stride) {
+    constexpr uint32_t kPer = 16u / sizeof(E);    // elements per piece
+    constexpr uint32_t kStep = 64u * kPer;        // elements per store instruction of the wave
+    if constexpr (!STRIDED) {
+        const uint32_t total = cnt * XY;
+        // 16-B stores need both runs 16-B aligned (true whenever N * XY % 4 == 0)
+        const bool vec = (((reinterpret_cast<uintptr_t>(vout) | reinterpret_cast<uintptr_t>(aout)) & 15u) == 0);
+        uint32_t f = kPer * lane;                     // first entry of this lane's piece
+        uint32_t l = f / XY, c = f - l * XY;          // its env and cell
+        const uint32_t dl = kStep / XY, dc = kStep - dl * XY;   // a 64-piece stride in envs / cells
+        for (; f < total; f += kStep) {
+            uint32_t vv[kPer], aa[kPer];
+            uint32_t ll = l, cc = c;
+#pragma unroll
+            for (uint32_t k = 0; k < kPer; ++k) {
+                obs_cell<W>(ow, lut, ll, cc, one, vv[k], aa[k]);
+                ++cc;
+                if (cc == XY) {
+                    cc = 0;
+                    ++ll;
+                }
+            }
+            if (vec && f + kPer <= total) {
+                if (vout) __builtin_nontemporal_store(obs_piece<E>(vv), reinterpret_cast<u32x4*>(vout + f));
+                if (aout) __builtin_nontemporal_store(obs_piece<E>(aa), reinterpret_cast<u32x4*>(aout + f));
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < kPer; ++k) {
+                    if (f + k < total) {
+                        if (vout) vout[f + k] = (E)vv[k];
+                        if (aout) aout[f + k] = (E)aa[k];
+                    }
+                }
+            }
+            c += dc;
+            l += dl;
+            if (c >= XY) {
+                c -= XY;
+                ++l;
+            }
+        }
+    } else {
+        if (vout) obs_write_plane<W, E, false>(ow, lut, lane, cnt, XY, vout, one, stride);
+        if (aout) obs_write_plane<W, E, true>(ow, lut, lane, cnt, XY, aout, one, stride);
+    }
+}
+
+template <int W>
+__device__ __forceinline__ void obs_write(const ObsWave<W>* ow, const uint16_t* lut, uint32_t lane, uint32_t cnt,
+                                          uint32_t XY, int32_t* __restrict__ vout, int32_t* __restrict__ aout) {
+    obs_write_as<W, uint32_t, false>(ow, lut, lane, cnt, XY, reinterpret_cast<uint32_t*>(vout),
+                                     reinterpret_cast<uint32_t*>(aout), 1u, 0);
 }
 
 // Bit-stream staging (k_rollout_obsw on multi-word pools, whose board bit x * pitch + y IS plane
@@ -348,38 +437,49 @@ __device__ __forceinline__ void obs_stage_stream(ObsStream<W>* os, uint32_t lane
 }
 
 // the staged envs [0, cnt) -> planes at vout / aout (run starts); zeroes the words it read.
-// Every lane of the writing wave calls this (wave-uniform)
-template <int W>
-__device__ __forceinline__ void obs_write_stream(ObsStream<W>* os, uint32_t lane, uint32_t cnt, uint32_t XY,
-                                                 int32_t* __restrict__ vout, int32_t* __restrict__ aout) {
+// Every lane of the writing wave calls this (wave-uniform).  E, one: as obs_write_as; a piece's
+// 16 / sizeof(E) entries are that many bits of one 32-bit word
+template <int W, class E>
+__device__ __forceinline__ void obs_write_stream_as(ObsStream<W>* os, uint32_t lane, uint32_t cnt, uint32_t XY,
+                                                    E* __restrict__ vout, E* __restrict__ aout, uint32_t one) {
+    constexpr uint32_t kPer = 16u / sizeof(E);
     const uint32_t total = cnt * XY;
     const bool vec = (((reinterpret_cast<uintptr_t>(vout) | reinterpret_cast<uintptr_t>(aout)) & 15u) == 0);
-    for (uint32_t f = 4u * lane; f < total; f += 256u) {
+    for (uint32_t f = kPer * lane; f < total; f += 64u * kPer) {
         const uint32_t wv = os->vis[f >> 5], wa = os->ag[f >> 5], sh = f & 31u;
-        uint32_t vv[4], aa[4];
+        uint32_t vv[kPer], aa[kPer];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            vv[k] = __builtin_amdgcn_ubfe(wv, sh + k, 1u);
-            aa[k] = __builtin_amdgcn_ubfe(wa, sh + k, 1u);
+        for (uint32_t k = 0; k < kPer; ++k) {
+            vv[k] = (0u - __builtin_amdgcn_ubfe(wv, sh + k, 1u)) & one;
+            aa[k] = (0u - __builtin_amdgcn_ubfe(wa, sh + k, 1u)) & one;
         }
-        if (sh == 0u) {   // after the reads of all 8 lanes of this word (in order within the wave)
+        if (sh == 0u) {   // after the reads of all the lanes of this word (in order within the wave)
             os->vis[f >> 5] = 0u;
             os->ag[f >> 5] = 0u;
         }
-        if (vec && f + 4u <= total) {
-            if (vout) __builtin_nontemporal_store(u32x4{vv[0], vv[1], vv[2], vv[3]}, reinterpret_cast<u32x4*>(vout + f));
-            if (aout) __builtin_nontemporal_store(u32x4{aa[0], aa[1], aa[2], aa[3]}, reinterpret_cast<u32x4*>(aout + f));
+        if (vec && f + kPer <= total) {
+            if (vout) __builtin_nontemporal_store(obs_piece<E>(vv), reinterpret_cast<u32x4*>(vout + f));
+            if (aout) __builtin_nontemporal_store(obs_piece<E>(aa), reinterpret_cast<u32x4*>(aout + f));
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
+            for (uint32_t k = 0; k < kPer; ++k) {
                 if (f + k < total) {
-                    if (vout) vout[f + k] = (int32_t)vv[k];
-                    if (aout) aout[f + k] = (int32_t)aa[k];
+                    if (vout) vout[f + k] = (E)vv[k];
+                    if (aout) aout[f + k] = (E)aa[k];
                 }
             }
         }
     }
 }
+template <int W>
+__device__ __forceinline__ void obs_write_stream(ObsStream<W>* os, uint32_t lane, uint32_t cnt, uint32_t XY,
+                                                 int32_t* __restrict__ vout, int32_t* __restrict__ aout) {
+    obs_write_stream_as<W, uint32_t>(os, lane, cnt, XY, reinterpret_cast<uint32_t*>(vout),
+                                     reinterpret_cast<uint32_t*>(aout), 1u);
+}
+
+// the observation planes of state records (k_observe_rec), on the staging and writers above
+#include "sparc_observe.hpp"
 
 // step() + the 'new' observation in one launch (SPaRCVecEnv.step): the gym one-call-per-step
 // contract with the planes, the puzzle index and the agent (x | y << 8) of every env
@@ -1953,6 +2053,7 @@ struct AuditCall {
 struct PuzzleDev {
     uint32_t num_puzzles = 0, num_nodes = 0;
     std::vector<uint4> h_info;         // host copy of t_info (the device rows)
+    uint32_t x_max = 0, y_max = 0;     // the largest lattice of the table (sparc_observe_records_device)
     DevBuf<uint64_t> open, init;
     DevBuf<uint4> info, root, trie, row1;
     DevBuf<uint2> trie8;               // split-kernel tables (empty: a puzzle's trie exceeds 15-bit nodes)
@@ -2041,6 +2142,7 @@ struct Ctx {
     DevBuf<uint8_t> fk_rec;
     DevBuf<uint32_t> fk_idx;
     // sparc_expand_host (sparc_expand.hpp): the children, and reward [4M] | flags [4M] | parent flags [M]
+    // (sparc_observe_records_host shares these: ex_child takes the two plane arrays, ex_out the scalars)
     DevBuf<uint8_t> ex_child, ex_out;
     // sparc_playout_host (sparc_playout.hpp): the per-playout outputs and the trace, the stats
     DevBuf<uint8_t> po_out;
@@ -2327,9 +2429,9 @@ int sparc_sync(void* ctx) {
         if (e & kErrJoin) return fail(c, SPARC_E_STATE, "rule rollout: an audit wave pair did not join (outputs unreliable)");
         if (e & kErrSnapshot)
             return fail(c, SPARC_E_INVALID,
-                        "snapshot / restore / fork / expand / playout / replay / records audit: index or record out of range "
-                        "(those "
-                        "envs unchanged, the children of those parents zeroed, the bits of those records 0)");
+                        "snapshot / restore / fork / expand / playout / replay / observe / records audit: index or record out "
+                        "of range (those "
+                        "envs unchanged, the children of those parents zeroed, the bits and planes of those records 0)");
         return fail(c, SPARC_E_INVALID, "device-side puzzle index out of range in a reset");
     }
     return SPARC_OK;
@@ -2374,6 +2476,10 @@ int sparc_load_puzzles(void* ctx, const sparc_puzzle_table* t) {
     d.num_puzzles = h.num_puzzles;
     d.num_nodes = h.num_nodes;
     d.h_info = std::move(h.info);
+    for (const uint4& r : d.h_info) {
+        d.x_max = std::max(d.x_max, r.x & 0xFFu);
+        d.y_max = std::max(d.y_max, (r.x >> 8) & 0xFFu);
+    }
     d.mixed_pays = h.mixed_pays;
     d.nodes8 = std::move(h.nodes8);
     d.sgeom = h.sgeom;
@@ -3593,6 +3699,97 @@ int sparc_expand_host(void* ctx, const sparc_snapshot_info* info, const void* re
     if (reward) HIPCHK(c, hipMemcpyAsync(reward, o, 4 * m, hipMemcpyDeviceToHost, c->stream));
     if (flags) HIPCHK(c, hipMemcpyAsync(flags, o + 4 * m, 4 * m, hipMemcpyDeviceToHost, c->stream));
     if (parent_flags) HIPCHK(c, hipMemcpyAsync(parent_flags, o + 8 * m, m, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
+}
+
+// ---- observation planes of records (sparc_observe.hpp): reads the context's tables only
+static int check_observe_args(Ctx* c, const sparc_snapshot_info* info, const void* records, int64_t M,
+                              const sparc_observe_out* out, bool device, uint32_t& bytes, uint32_t& one) {
+    int rc = check_snapshot_info(c, info);
+    if (rc) return rc;
+    if (!records) return fail(c, SPARC_E_INVALID, "null records");
+    if (device && (reinterpret_cast<uintptr_t>(records) & 15u)) return fail(c, SPARC_E_INVALID, "records must be 16-B aligned");
+    if ((rc = check_record_count(c, M, false))) return rc;
+    if (!out) return fail(c, SPARC_E_INVALID, "null out");
+    switch (out->elem) {
+        case SPARC_OBS_I32: bytes = 4, one = 1u; break;
+        case SPARC_OBS_U8: bytes = 1, one = 1u; break;
+        case SPARC_OBS_F16: bytes = 2, one = 0x3C00u; break;
+        case SPARC_OBS_BF16: bytes = 2, one = 0x3F80u; break;
+        case SPARC_OBS_F32: bytes = 4, one = 0x3F800000u; break;
+        default: return fail(c, SPARC_E_INVALID, "out: elem must be one of SPARC_OBS_*");
+    }
+    if (!out->visited && !out->agent && !out->puzzle && !out->loc && !out->legal)
+        return fail(c, SPARC_E_INVALID, "out: at least one output is needed");
+    if (out->x_dim < (int32_t)c->pz.x_max || out->y_dim < (int32_t)c->pz.y_max)
+        return fail(c, SPARC_E_INVALID, "out: x_dim and y_dim must not be below the table's largest x_size and y_size");
+    if ((rc = check_obs_dims(c, out->x_dim, out->y_dim))) return rc;
+    if (out->stride < 0 || (out->stride > 0 && out->stride < (int64_t)out->x_dim * out->y_dim))
+        return fail(c, SPARC_E_INVALID, "out: stride must be 0 (dense) or at least x_dim * y_dim");
+    if (device && ((reinterpret_cast<uintptr_t>(out->visited) | reinterpret_cast<uintptr_t>(out->agent)) & (bytes - 1u)))
+        return fail(c, SPARC_E_INVALID, "out: visited and agent must be aligned to their element");
+    return SPARC_OK;
+}
+
+int sparc_observe_records_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M,
+                                 const sparc_observe_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    uint32_t bytes = 0, one = 0;
+    if ((rc = check_observe_args(c, info, d_records, M, out, true, bytes, one))) return rc;
+    const Params p = make_params(c);
+    const ObserveOut o{out->visited, out->agent, (uint32_t)out->x_dim, (uint32_t)out->y_dim, (uint64_t)out->stride, one,
+                       out->puzzle, out->loc, out->legal};
+    const uint4* rec = static_cast<const uint4*>(d_records);
+    const uint32_t m = (uint32_t)M;
+    dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
+        constexpr int kW = decltype(w)::value;
+        constexpr bool kTb = decltype(tb)::value;
+        if (bytes == 4) k_observe_rec<kW, kTb, uint32_t><<<grid_for(m), kSnapBlock, 0, c->stream>>>(p, rec, m, o);
+        else if (bytes == 2) k_observe_rec<kW, kTb, uint16_t><<<grid_for(m), kSnapBlock, 0, c->stream>>>(p, rec, m, o);
+        else k_observe_rec<kW, kTb, uint8_t><<<grid_for(m), kSnapBlock, 0, c->stream>>>(p, rec, m, o);
+    });
+    return launch_check(c);
+}
+
+int sparc_observe_records_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M,
+                               const sparc_observe_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    uint32_t eb = 0, one = 0;
+    if ((rc = check_observe_args(c, info, records, M, out, false, eb, one))) return rc;
+    // staged in the expand call's buffers: records | visited, agent (dense or at the caller's
+    // stride) | puzzle [M], loc [M][2], legal [M]
+    const size_t m = (size_t)M, rbytes = (size_t)info->record_bytes * m;
+    const size_t xy = (size_t)out->x_dim * out->y_dim, st = out->stride ? (size_t)out->stride : xy;
+    const size_t pl = (((m - 1) * st + xy) * eb + 15) / 16 * 16;   // one plane array, to its last element
+    HIPCHK(c, c->fk_rec.reserve(rbytes));
+    HIPCHK(c, c->ex_child.reserve(2 * pl));
+    HIPCHK(c, c->ex_out.reserve(13 * m));
+    uint8_t* dp = c->ex_child.get();
+    uint8_t* ds = c->ex_out.get();
+    HIPCHK(c, hipMemcpyAsync(c->fk_rec.get(), records, rbytes, hipMemcpyHostToDevice, c->stream));
+    sparc_observe_out d = *out;
+    d.visited = out->visited ? dp : nullptr;
+    d.agent = out->agent ? dp + pl : nullptr;
+    d.puzzle = out->puzzle ? reinterpret_cast<uint32_t*>(ds) : nullptr;
+    d.loc = out->loc ? reinterpret_cast<int32_t*>(ds + 4 * m) : nullptr;
+    d.legal = out->legal ? ds + 12 * m : nullptr;
+    if ((rc = sparc_observe_records_device(c, info, c->fk_rec.get(), M, &d))) return rc;
+    // only the planes travel back: what lies between them in the caller's array stays as it is
+    auto planes_back = [&](void* dst, const uint8_t* src) -> hipError_t {
+        if (st == xy) return hipMemcpyAsync(dst, src, m * xy * eb, hipMemcpyDeviceToHost, c->stream);
+        return hipMemcpy2DAsync(dst, st * eb, src, st * eb, xy * eb, m, hipMemcpyDeviceToHost, c->stream);
+    };
+    if (out->visited) HIPCHK(c, planes_back(out->visited, dp));
+    if (out->agent) HIPCHK(c, planes_back(out->agent, dp + pl));
+    if (out->puzzle) HIPCHK(c, hipMemcpyAsync(out->puzzle, ds, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    if (out->loc) HIPCHK(c, hipMemcpyAsync(out->loc, ds + 4 * m, 8 * m, hipMemcpyDeviceToHost, c->stream));
+    if (out->legal) HIPCHK(c, hipMemcpyAsync(out->legal, ds + 12 * m, m, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 

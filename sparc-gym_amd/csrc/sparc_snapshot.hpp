@@ -47,6 +47,38 @@ __host__ __device__ constexpr int snap_record_bytes(int W, bool tb) {
     return (((4 + 2 * W + (tb ? 4 * W : 0)) + 3) & ~3) * 4;
 }
 
+// The legal actions (_get_legal_actions, SPaRC_Gym.py:1024-1051; a 4-bit mask in action order) of
+// the state of a VALIDATED record, from its board as Env::load finds them: pos and pid are the
+// record's words, vis its visited board, `last` the path's last move (move len - 2 of the
+// direction stack; only read under traceback with len >= 2, where the one legal revisit is its
+// reverse).  k_restore's flags and k_observe_rec's legal byte.
+template <int W, bool TB>
+__device__ __forceinline__ uint32_t record_legal(const Params& p, uint32_t pos, uint32_t pid, const uint64_t (&vis)[W],
+                                                 uint32_t last) {
+    const uint32_t x = pos & 0xFFu, y = (pos >> 8) & 0xFFu, len = (pos >> 16) & 0xFFu;
+    const PuzzleSrc<W> ps{p.tab.info, p.tab.root, p.tab.open, p.tab.init, p.tab.row1};
+    Env<W, TB> e;
+    if constexpr (W == 1) {
+        const uint32_t P = p.pitch;
+        e.e = x * P + y;
+        e.len = len;
+        e.load_puzzle(ps, pid);
+        e.fr = (p.tab.open[pid] & ~vis[0]) << P;
+        e.rl = (TB && len >= 2u) ? (last ^ 2u) : 0u;   // the stack in registers holds reversed moves
+        return e.legal_mask(P);
+    } else {
+#pragma unroll
+        for (int k = 0; k < W; ++k) e.vis[k] = vis[k];
+        e.x = x;
+        e.y = y;
+        e.len = len;
+        uint32_t sx, sy;
+        e.load_puzzle(ps, pid, sx, sy);
+        e.last = (TB && len >= 2u) ? last : 0u;
+        return e.legal_mask(p.pitch);
+    }
+}
+
 // Record j <- env env[j] (env NULL: env j) for j < M.  A record whose env index is not below N
 // (error bit raised) is written as zeros: len 0, which no restore accepts.
 template <int W, bool TB>
@@ -170,37 +202,18 @@ __global__ void __launch_bounds__(kSnapBlock) k_restore(Params p, const uint4* _
     s.step[i] = w[2];
     s.pid[i] = pid;
     if (!flg) return;
-    // the legal actions of the restored state, from the restored board as Env::load finds them
-    const PuzzleSrc<W> ps{p.tab.info, p.tab.root, p.tab.open, p.tab.init, p.tab.row1};
-    Env<W, TB> e;
-    uint32_t legal;
-    if constexpr (W == 1) {
-        const uint32_t P = p.pitch;
-        e.e = x * P + y;
-        e.len = len;
-        e.load_puzzle(ps, pid);
-        e.fr = (p.tab.open[pid] & ~vis[0]) << P;
-        e.rl = 0;
-        if constexpr (TB) {
-            e.stk.lo = dirs[0] ^ kRev2;
-            e.stk.hi = dirs[1] ^ kRev2;
-            e.rl = len >= 2u ? e.stk.read(len - 2u) : 0u;
+    // the last move of the path (move len - 2), which the traceback rule needs
+    uint32_t last = 0;
+    if constexpr (TB) {
+        if (len >= 2u) {
+            const uint32_t k = len - 2u;
+            uint64_t dw = 0;
+#pragma unroll
+            for (int j = 0; j < 2 * W; ++j) dw |= dirs[j] & ((k >> 5) == (uint32_t)j ? ~0ull : 0ull);
+            last = (uint32_t)(dw >> ((k & 31u) * 2u)) & 3u;
         }
-        legal = e.legal_mask(P);
-    } else {
-#pragma unroll
-        for (int k = 0; k < W; ++k) e.vis[k] = vis[k];
-#pragma unroll
-        for (int k = 0; k < (TB ? 2 * W : 1); ++k) e.dirs[k] = dirs[k];
-        e.x = x;
-        e.y = y;
-        e.len = len;
-        uint32_t sx, sy;
-        e.load_puzzle(ps, pid, sx, sy);
-        e.last = (TB && len >= 2u) ? e.dir_at(len - 2u) : 0u;
-        legal = e.legal_mask(p.pitch);
     }
-    flg[i] = (uint8_t)(legal << 2);
+    flg[i] = (uint8_t)(record_legal<W, TB>(p, pos, pid, vis, last) << 2);
 }
 
 }  // namespace sparc

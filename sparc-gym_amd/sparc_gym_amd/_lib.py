@@ -86,6 +86,20 @@ class SparcReplayOut(ctypes.Structure):
                                         "final_rec", "states")]
 
 
+# SPARC_OBS_*: the element type of sparc_observe_records_device's planes
+OBS_I32, OBS_U8, OBS_F16, OBS_BF16, OBS_F32 = range(5)
+OBS_ELEM_BYTES = {OBS_I32: 4, OBS_U8: 1, OBS_F16: 2, OBS_BF16: 2, OBS_F32: 4}
+
+
+class SparcObserveOut(ctypes.Structure):
+    """sparc_observe_out: the outputs of sparc_observe_records_device / _host, each pointer may be NULL."""
+    _fields_ = [("visited", c_void_p), ("agent", c_void_p), ("elem", c_int32), ("x_dim", c_int32),
+                ("y_dim", c_int32), ("reserved", c_int32), ("stride", ctypes.c_int64), ("puzzle", c_void_p),
+                ("loc", c_void_p), ("legal", c_void_p)]
+
+
+assert ctypes.sizeof(SparcObserveOut) == 64
+
 # SPARC_DFS_*: the status of a record's walk after sparc_dfs_device
 DFS_INVALID, DFS_COMPLETE, DFS_BUDGET, DFS_PENDING, DFS_OVERFLOW = range(5)
 # the columns of its counters
@@ -155,6 +169,10 @@ _SIGS = {
                              c_void_p, c_void_p, ctypes.c_uint32, ctypes.POINTER(SparcReplayOut)], c_int32),
     "sparc_replay_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, c_void_p, ctypes.c_int64, c_int32,
                            c_void_p, c_void_p, ctypes.c_uint32, ctypes.POINTER(SparcReplayOut)], c_int32),
+    "sparc_observe_records_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64,
+                                      ctypes.POINTER(SparcObserveOut)], c_int32),
+    "sparc_observe_records_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64,
+                                    ctypes.POINTER(SparcObserveOut)], c_int32),
     "sparc_dfs_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, ctypes.c_uint32,
                           c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
     "sparc_dfs_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, ctypes.c_uint32,

@@ -320,6 +320,55 @@ class SparcCore:
                                                _ptr(flags), _ptr(pflags)))
         return children, rew, flags, pflags
 
+    # ---------------------------------------------------------------- observation planes of records
+    def _check_observe(self, M, elem, x_dim, y_dim, stride, outputs):
+        """The argument rules of sparc_observe_records_device that need no device (ValueError)."""
+        if elem not in _lib.OBS_ELEM_BYTES:
+            raise ValueError("elem must be one of the OBS_* element types")
+        if not 1 <= M < 2**31:
+            raise ValueError("M must be in 1..2^31-1")
+        if x_dim < self.table.x_max or y_dim < self.table.y_max or x_dim * y_dim > 256:
+            raise ValueError(f"x_dim, y_dim must be at least {self.table.x_max}, {self.table.y_max} (the table's "
+                             "largest lattice) with x_dim * y_dim <= 256")
+        if stride < 0 or 0 < stride < x_dim * y_dim:
+            raise ValueError("stride must be 0 (dense) or at least x_dim * y_dim")
+        if all(x is None for x in outputs):
+            raise ValueError("out: at least one output is needed")
+
+    def observe_records_device(self, info, d_records, M, elem=_lib.OBS_I32, x_dim=None, y_dim=None, stride=0,
+                               d_visited=None, d_agent=None, d_puzzle=None, d_loc=None, d_legal=None):
+        """sparc_observe_records_device: the visited / agent_location planes of M records
+        ([x_dim][y_dim] elements of type ``elem``, ``stride`` elements apart, 0: dense), the puzzle
+        index [M] uint32, the agent's (x, y) [M][2] int32 and the legal actions [M] uint8, each may
+        be None; reads the context's tables only (asynchronous)."""
+        M, elem, stride = int(M), int(elem), int(stride)
+        x_dim = self.table.x_max if x_dim is None else int(x_dim)
+        y_dim = self.table.y_max if y_dim is None else int(y_dim)
+        self._check_observe(M, elem, x_dim, y_dim, stride, (d_visited, d_agent, d_puzzle, d_loc, d_legal))
+        out = _lib.SparcObserveOut(d_visited, d_agent, elem, x_dim, y_dim, 0, stride, d_puzzle, d_loc, d_legal)
+        self._check(self.lib.sparc_observe_records_device(self.ctx, ctypes.byref(info), d_records, M,
+                                                          ctypes.byref(out)))
+
+    def observe_records_host(self, info, records, elem=_lib.OBS_I32, x_dim=None, y_dim=None):
+        """Observe host records [M, record_bytes]: a dict of host arrays ``visited`` and ``agent``
+        [M, x_dim, y_dim] (the element's bytes as uint8 / uint16 / uint32 for 1 / 2 / 4-byte
+        elements; int32 for OBS_I32), ``puzzle`` [M] uint32, ``loc`` [M, 2] int32 and ``legal`` [M]
+        uint8 (synchronous)."""
+        rec = np.ascontiguousarray(records, np.uint8)
+        if rec.ndim != 2 or rec.shape[1] != info.record_bytes or len(rec) < 1:
+            raise ValueError(f"records must be [M, {info.record_bytes}] uint8 with M >= 1")
+        M, elem = len(rec), int(elem)
+        x_dim = self.table.x_max if x_dim is None else int(x_dim)
+        y_dim = self.table.y_max if y_dim is None else int(y_dim)
+        self._check_observe(M, elem, x_dim, y_dim, 0, (True,))
+        dt = np.int32 if elem == _lib.OBS_I32 else {1: np.uint8, 2: np.uint16, 4: np.uint32}[_lib.OBS_ELEM_BYTES[elem]]
+        out = {"visited": np.empty((M, x_dim, y_dim), dt), "agent": np.empty((M, x_dim, y_dim), dt),
+               "puzzle": np.empty(M, np.uint32), "loc": np.empty((M, 2), np.int32), "legal": np.empty(M, np.uint8)}
+        o = _lib.SparcObserveOut(_ptr(out["visited"]), _ptr(out["agent"]), elem, x_dim, y_dim, 0, 0,
+                                 _ptr(out["puzzle"]), _ptr(out["loc"]), _ptr(out["legal"]))
+        self._check(self.lib.sparc_observe_records_host(self.ctx, ctypes.byref(info), _ptr(rec), M, ctypes.byref(o)))
+        return out
+
     # ---------------------------------------------------------------- legal-move playouts of records
     def playout_device(self, info, d_records, M, K, L, seed=0, id0=0, flags=0, d_code=None, d_flags=None,
                        d_steps=None, d_first=None, d_end=None, d_return=None, d_trace=None, d_final=None,

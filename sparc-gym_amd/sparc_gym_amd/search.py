@@ -265,6 +265,81 @@ def score_paths(vec, puzzle_indices, paths, as_points=False):
             "satisfied": (bits & RULE_ALL) != 0}
 
 
+def solution_dataset(vec, puzzle_indices=None, dtype=torch.uint8):
+    """The behaviour-cloning set of the listed solutions: one row per move of every path of
+    ``vec.puzzles[q]['solution_paths']`` for ``q`` in ``puzzle_indices`` (default: every puzzle),
+    the observation of the state BEFORE the move with the move as its label.  A path is taken when
+    it starts at the puzzle's start and consists of unit moves (``actions_from_points``); the
+    taken paths are walked in ONE ``vec.replay`` launch from ``vec.roots`` with ``states=True`` (both
+    stop flags: a path that replay does not walk to its last point is left out), the record before
+    each action (the root, then the states) is gathered, and ONE ``vec.observe`` turns them into
+    planes of ``dtype``.  Touches no env and does not depend on ``vec.num_envs``.
+
+    Returns a dict: the observation of ``vec.observe`` over the R rows (``visited``,
+    ``agent_location`` [R, x_dim, y_dim], ``puzzle_index``, ``agent_xy``, ``legal_actions``),
+    ``action`` [R] uint8 the move taken from that state, ``path`` and ``t`` [R] int64 (which kept
+    path, which of its moves; rows are ordered by path, then t), all GPU tensors, and on the host
+    ``paths``: per kept path ``(puzzle index, index in its solution list)``, and ``skipped``: the
+    counts of listed paths left out, by reason (``wrong_start``, ``non_unit_move``, ``refused``).
+    With no move to learn from (no kept path longer than one point) the tensors are None."""
+    from .snapshot import Snapshot
+    P = len(vec.puzzles)
+    qs = np.arange(P) if puzzle_indices is None else np.asarray(puzzle_indices, np.int64).reshape(-1)
+    if len(qs) and (int(qs.min()) < 0 or int(qs.max()) >= P):
+        raise ValueError(f"puzzle_indices must be in 0..{P - 1}")
+    skipped = {"wrong_start": 0, "non_unit_move": 0, "refused": 0}
+    cand = []                                            # (puzzle, index in its list, actions)
+    for q in qs.tolist():
+        p = vec.puzzles[q]
+        for s, pts in enumerate(p["solution_paths"]):
+            acts, ok = actions_from_points(p["start_location"], pts)
+            if not ok:
+                skipped["wrong_start"] += 1
+            elif (acts == ILLEGAL_ACTION).any():
+                skipped["non_unit_move"] += 1
+            else:
+                cand.append((q, s, acts))
+    empty = {k: None for k in ("visited", "agent_location", "puzzle_index", "agent_xy", "legal_actions", "action",
+                               "path", "t")}
+    walk = [c for c in cand if len(c[2])]                # a one-point path has no move: kept, no row
+    kept = [c for c in cand if not len(c[2])]
+    if walk:
+        K = len(walk)
+        lengths = np.array([len(c[2]) for c in walk], np.int64)
+        L = int(lengths.max())
+        actions = np.full((L, K), ILLEGAL_ACTION, np.uint8)
+        for k, c in enumerate(walk):
+            actions[:len(c[2]), k] = c[2]
+        roots = vec.roots(np.array([c[0] for c in walk], np.int64))
+        out = vec.replay(roots, actions, lengths=lengths, stop_done=True, stop_illegal=True, final=False,
+                         states=True)
+        walked = out["steps"].cpu().numpy().astype(np.int64) == lengths
+        skipped["refused"] = int((~walked).sum())
+        good = np.nonzero(walked)[0]
+        kept += [walk[k] for k in good]
+    else:
+        good = np.zeros(0, np.int64)
+    paths = [(c[0], c[1]) for c in kept]
+    if not len(good):
+        return {**empty, "paths": paths, "skipped": skipped}
+    first = len(kept) - len(good)                        # the kept paths without a move come first
+    n = lengths[good]
+    path = np.repeat(np.arange(len(good)), n)
+    t = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+    col = good[path]
+    # the record before action t of sequence col: root col (t = 0), else states row (t - 1) * K + col
+    row = np.where(t == 0, col, K + (t - 1) * K + col)
+    snap = Snapshot.cat([roots, out["states"]]).select(row)
+    obs = vec.observe(snap, dtype=dtype)
+    dev = obs["visited"].device
+    obs["action"] = torch.from_numpy(actions[t, col].copy()).to(dev)
+    obs["path"] = torch.from_numpy(path + first).to(dev)
+    obs["t"] = torch.from_numpy(t).to(dev)
+    obs["paths"] = paths
+    obs["skipped"] = skipped
+    return obs
+
+
 def solve_dfs(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, undecided=65536):
     """Every self-avoiding path from the start of each of ``puzzle_indices`` (one root per entry:
     that puzzle's reset state, all roots at once) counted with the puzzle's own verdict, as

@@ -37,6 +37,10 @@ its episode or L steps, again in one launch without an env, with per-root statis
 (``search.monte_carlo``).  ``replay(snap, actions, lengths)`` plays action sequences that the caller
 supplies, from records or (``puzzle_indices``) from puzzles' reset states, again in one launch without
 an env; ``roots(puzzle_indices)`` gives reset states as records (``search.score_paths``).
+``observe(snap, dtype, out, channels)`` returns the observation ``step()`` returns for records instead
+of envs: the ``visited`` and ``agent_location`` planes in the network's dtype, optionally straight
+into two channels of the network's input tensor, with ``puzzle_index``, ``agent_xy`` and
+``legal_actions``, again in one launch without an env (``search.solution_dataset``).
 """
 from __future__ import annotations
 
@@ -210,7 +214,92 @@ class _RecordReplay:
         return self.replay(puzzle_indices=puzzle_indices)["final"]
 
 
-class SPaRCVecEnv(_RecordReplay):
+OBS_DTYPES = {torch.int32: _lib.OBS_I32, torch.uint8: _lib.OBS_U8, torch.float16: _lib.OBS_F16,
+              torch.bfloat16: _lib.OBS_BF16, torch.float32: _lib.OBS_F32}
+
+
+class _RecordObserve:
+    """``observe`` of ``SPaRCVecEnv``: the observation of records instead of envs.  A base class of
+    its own for the reason ``_RecordReplay`` is one; tests/test_observe_guards.py and
+    tests/test_gpu_observe.py check the stream contract for it."""
+
+    def observe(self, snap, dtype=torch.int32, out=None, channels=None):
+        """The observation ``step()`` returns (_get_obs, SPaRC_Gym.py:956-979), for the records of
+        ``snap`` instead of envs, in one launch and without changing or reading any env
+        (k_observe_rec): the input of a policy or value network over a search frontier, the
+        children of ``expand`` or the ``states`` of ``replay``.
+
+        Returns a dict of GPU tensors: ``visited`` and ``agent_location`` [M, x_dim, y_dim] of
+        ``dtype`` (int32, the reference's; uint8, float16, bfloat16 or float32: 1 / 1.0 and 0), bit
+        for bit the planes ``restore`` of the records into M envs and ``reset``'s observation give;
+        ``puzzle_index`` [M] int32 (``static_planes[puzzle_index]`` are the static planes);
+        ``agent_xy`` [M, 2] int32; ``legal_actions`` [M] uint8, bit a set when action a is legal in
+        the record's state (``info['legal_actions']`` of ``restore``).  A pending record is observed
+        as it stands.
+
+        ``out``: a contiguous [M, C, x_dim, y_dim] tensor of ``dtype`` on this env's device, with
+        ``channels=(c_visited, c_agent)``: the two planes are written straight into those channels
+        of it (the network's input, assembled without a copy), the returned planes are views of
+        them, and no other byte of ``out`` is touched.
+
+        A record that fails the kernel's checks gets all-zero planes, ``puzzle_index`` -1,
+        ``agent_xy`` (0, 0) and ``legal_actions`` 0, and the next ``core.sync()`` raises.
+        ValueError: an unsupported ``dtype``, ``out`` without ``channels`` or the reverse, a shape,
+        dtype, device or layout mismatch of ``out``, equal or out-of-range channels, a snapshot
+        header that does not match this env (naming the field)."""
+        from .snapshot import info_mismatch
+        self._stream()
+        if dtype not in OBS_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(str(d) for d in OBS_DTYPES)}, not {dtype}")
+        M = len(snap)
+        if not 1 <= M < 2**31:
+            raise ValueError("snap must hold 1 .. 2^31 - 1 records")
+        X, Y = self.x_dim, self.y_dim
+        if (out is None) != (channels is None):
+            raise ValueError("out and channels are given together or not at all")
+        if out is not None:
+            if not isinstance(out, torch.Tensor):
+                raise ValueError("out must be a tensor")
+            if out.dtype != dtype:
+                raise ValueError(f"out must have dtype {dtype}, not {out.dtype}")
+            if out.device != self.device:
+                raise ValueError(f"out must be on device {self.device}, not {out.device}")
+            if out.ndim != 4 or out.shape[0] != M or out.shape[1] < 2 or tuple(out.shape[2:]) != (X, Y):
+                raise ValueError(f"out must have shape [{M}, C >= 2, {X}, {Y}], not {list(out.shape)}")
+            if not out.is_contiguous():
+                raise ValueError("out must be contiguous")
+            try:
+                cv, ca = (int(c) for c in channels)
+            except (TypeError, ValueError):
+                raise ValueError("channels must be two integers (c_visited, c_agent)") from None
+            C = int(out.shape[1])
+            if not (0 <= cv < C and 0 <= ca < C) or cv == ca:
+                raise ValueError(f"channels must be two different values in 0..{C - 1}")
+        info = self.core.snapshot_info()
+        bad = info_mismatch(snap.info, info)
+        if bad is not None:
+            raise ValueError(f"snapshot does not match this env: {bad} differs")
+        rec = snap.records
+        if not isinstance(rec, torch.Tensor):
+            rec = torch.from_numpy(np.ascontiguousarray(rec, np.uint8))
+        rec = rec.to(self.device).contiguous()
+        dev = self.device
+        if out is None:
+            planes = torch.empty((2, M, X, Y), dtype=dtype, device=dev)
+            vis, agent, stride = planes[0], planes[1], 0
+        else:
+            vis, agent, stride = out[:, cv], out[:, ca], C * X * Y
+        pidx = torch.empty(M, dtype=torch.int32, device=dev)
+        loc = torch.empty((M, 2), dtype=torch.int32, device=dev)
+        legal = torch.empty(M, dtype=torch.uint8, device=dev)
+        self.core.observe_records_device(snap.info, rec.data_ptr(), M, OBS_DTYPES[dtype], X, Y, stride,
+                                         d_visited=vis.data_ptr(), d_agent=agent.data_ptr(),
+                                         d_puzzle=pidx.data_ptr(), d_loc=loc.data_ptr(), d_legal=legal.data_ptr())
+        return {"visited": vis, "agent_location": agent, "puzzle_index": pidx, "agent_xy": loc,
+                "legal_actions": legal}
+
+
+class SPaRCVecEnv(_RecordReplay, _RecordObserve):
     def __init__(self, num_envs, puzzles=None, df_name="lkaesberg/SPaRC", df_split="all", df_set="test",
                  observation="new", traceback=False, max_steps=2000, autoreset="next_step", device=0,
                  env_offset=0, pitch=None, words=None, processed=None, table=None, rules=False, copy=True,

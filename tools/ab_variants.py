@@ -61,10 +61,10 @@ VARIANTS = {
     # the path rules' triangle count by v_bitop3 (audit_path)
     "tribitop": [("sparc_rules.hpp", '    // triangles: bit-sliced count of path neighbours (x±1: ±P, y±1: ±1)\n    const BB<W> a = vis.shr(P), b = vis.shl(P), c = vis.shr(1), d = vis.shl(1);\n    const BB<W> s1 = a ^ b, c1 = a & b, s2 = c ^ d, c2 = c & d;\n    const BB<W> n0 = s1 ^ s2, k0 = s1 & s2, n1 = c1 ^ c2 ^ k0, n2 = c1 & c2;\n    const BB<W> bad = pr.pl[kB_TRI] & ((n0 ^ pr.pl[kB_TRI0]) | (n1 ^ pr.pl[kB_TRI1]) | (n2 ^ pr.pl[kB_TRI2]));\n    const bool tri_ok = !bad.any();', '    // triangles: bit-sliced count of path neighbours (x±1: ±P, y±1: ±1) per 32-bit half, a full\n    // adder of a, b, c (sum s, carry M) plus d: bit 0 s ^ d, bit 1 M ^ (s & d), bit 2 M & s & d,\n    // each compared with the planes by v_bitop3 (7 per half against 13 plain logic VALU)\n    const BB<W> a = vis.shr(P), b = vis.shl(P), c = vis.shr(1), d = vis.shl(1);\n    uint32_t bad = 0;\n#pragma unroll\n    for (int h = 0; h < 2 * W; ++h) {\n        auto half = [h](const BB<W>& x) { return (uint32_t)(x.w[h >> 1] >> (32 * (h & 1))); };\n        const uint32_t ah = half(a), bh = half(b), ch = half(c), dh = half(d);\n        const uint32_t s = bitop3<0x96>(ah, bh, ch);                     // a ^ b ^ c\n        const uint32_t M = bitop3<0xE8>(ah, bh, ch);                     // majority (the carry)\n        const uint32_t e0 = bitop3<0x96>(s, dh, half(pr.pl[kB_TRI0]));   // count bit 0 ^ TRI0\n        const uint32_t n1 = bitop3<0x78>(M, s, dh);                      // M ^ (s & d)\n        const uint32_t n2 = bitop3<0x80>(M, s, dh);                      // M & s & d\n        const uint32_t f = bitop3<0xF6>(e0, n1, half(pr.pl[kB_TRI1]));   // e0 | (n1 ^ TRI1)\n        const uint32_t g = bitop3<0xF6>(f, n2, half(pr.pl[kB_TRI2]));    // f | (n2 ^ TRI2)\n        bad |= g & half(pr.pl[kB_TRI]);\n    }\n    const bool tri_ok = bad == 0u;'), ("sparc_rules.hpp", 'template <int W>\n__device__ __forceinline__ uint32_t audit_path(', '// v_bitop3_b32 d = TT[x << 2 | y << 1 | z] bitwise (gfx950)\ntemplate <uint32_t TT>\n__device__ __forceinline__ uint32_t bitop3(uint32_t x, uint32_t y, uint32_t z) {\n    uint32_t d;\n    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:%4" : "=v"(d) : "v"(x), "v"(y), "v"(z), "i"(TT));\n    return d;\n}\n\ntemplate <int W>\n__device__ __forceinline__ uint32_t audit_path(')],
     # the plane writer's piece loop unrolled twice (more stores in flight per wave)
-    "obsun2": [("sparc_kernels.hip", """    const uint32_t dl = 256u / XY, dc = 256u - dl * XY;   // a 64-piece stride in envs / cells
-    for (; f < total; f += 256u) {""", """    const uint32_t dl = 256u / XY, dc = 256u - dl * XY;   // a 64-piece stride in envs / cells
+    "obsun2": [("sparc_kernels.hip", """        const uint32_t dl = kStep / XY, dc = kStep - dl * XY;   // a 64-piece stride in envs / cells
+        for (; f < total; f += kStep) {""", """        const uint32_t dl = kStep / XY, dc = kStep - dl * XY;   // a 64-piece stride in envs / cells
 #pragma unroll 2
-    for (; f < total; f += 256u) {""")],
+        for (; f < total; f += kStep) {""")],
     # k_rollout1s with the move rows (mrow) read from global memory although the table fits LDS
     "mrowg": [("sparc_kernels.hip", """        mrow = lm;
         trow = lt;
