@@ -604,6 +604,58 @@ int sparc_observe_records_device(void *ctx, const sparc_snapshot_info *info, con
 int sparc_observe_records_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
                                const sparc_observe_out *out);
 
+/* ---- target reachability and distance maps of records: can this position still reach the target,
+ * and how far away is it ---------------------------------------------------------------------------
+ * A path is self-avoiding, so every move closes a lattice point for good, and a position whose free
+ * points no longer connect the agent to the target is lost whatever the rules say.  For each of M
+ * records (1 <= M < 2^31, independent of num_envs), in one launch and without touching an env: as
+ * with sparc_observe_records_device the context supplies its puzzle table, words and pitch only;
+ * sparc_load_puzzles is enough (no reset, no sparc_load_rules).  The reference has no counterpart.
+ * Of a record only the puzzle index, the agent's (x, y) and the visited board enter: not step,
+ * pending, max_steps, the trie state or the traceback mode; a pending record is answered as it
+ * stands.  With F the puzzle's lattice points that are no gap and not visited (the agent's own
+ * point is visited, so never free), C the 4-connected component of F that holds the target (empty
+ * when the target is not in F: the agent stands on it) and D(p) the breadth-first distance from p
+ * in C to the target, D(target) = 0:
+ *  dist         [M]     0 if the agent is on the target, else the minimum of action_dist, else
+ *                       SPARC_REACH_NONE: the moves still needed, a lower bound of any path's
+ *  action_dist  [M][4]  1 + D(n_a) if the neighbour n_a in direction a (the action order of
+ *                       sparc_step_device) lies in the lattice and in C, else SPARC_REACH_NONE.
+ *                       Exact for the child: child (j, a) of sparc_expand_device has
+ *                       dist == action_dist[a] - 1
+ *  live         [M]     bit a set iff action_dist[a] != SPARC_REACH_NONE: a subset of the forward
+ *                       legal moves (_get_legal_actions, SPaRC_Gym.py:1024-1051, without the
+ *                       traceback revisit), those after which the target can still be reached
+ *  size         [M]     |C|, at most 254
+ *  plane        [M][x_dim][y_dim], dense uint8: D on C, SPARC_REACH_NONE everywhere else, cells
+ *                       outside the puzzle's lattice included.  x_dim, y_dim: not below the
+ *                       table's largest x_size / y_size, x_dim * y_dim <= 256; read only when
+ *                       plane != NULL.  A typed or strided plane written straight into a network's
+ *                       channel is out of scope: convert or copy the dense plane.
+ * Every output may be NULL, at least one must not be.  info must match the context as for
+ * sparc_expand_device (SPARC_E_INVALID naming the field).  SPARC_E_INVALID, naming the argument and
+ * before any launch, also for: M outside 1 .. 2^31 - 1; d_records NULL or not 16-B aligned; with a
+ * plane, x_dim / y_dim below the table's maxima or x_dim * y_dim > 256.
+ * Every record is checked on the device before anything is indexed with it, with the conditions of
+ * sparc_restore_device.  A record that fails gets dist and action_dist SPARC_REACH_NONE, live 0,
+ * size 0 and a plane of SPARC_REACH_NONE, and sparc_sync reports the error; every other record is
+ * unaffected.  Device pointers, asynchronous on the context's stream. */
+#define SPARC_REACH_NONE 255
+typedef struct {
+    uint8_t *dist;         /* [M]                              */
+    uint8_t *action_dist;  /* [M][4]                           */
+    uint8_t *live;         /* [M] bits 0-3                     */
+    uint8_t *size;         /* [M]                              */
+    uint8_t *plane;        /* [M][x_dim][y_dim], dense         */
+    int32_t x_dim, y_dim;  /* read only when plane != NULL     */
+} sparc_reach_out;
+int sparc_reach_records_device(void *ctx, const sparc_snapshot_info *info, const void *d_records, int64_t M,
+                               const sparc_reach_out *out);
+/* the host-pointer form (records and every member of out on the host, no alignment requirement):
+ * staged through the context's stream, returns after the data have moved */
+int sparc_reach_records_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
+                             const sparc_reach_out *out);
+
 /* ---- rule audit: info['rule_status'] (_validate_rules, SPaRC_Gym.py:941-950) ----------------
  * Rule table, packed by sparc_gym_amd/puzzles.py:pack_rules from the processed puzzles, on the
  * step table's geometry (bit x*pitch + y, `words` u64 per board).

@@ -480,6 +480,8 @@ __device__ __forceinline__ void obs_write_stream(ObsStream<W>* os, uint32_t lane
 
 // the observation planes of state records (k_observe_rec), on the staging and writers above
 #include "sparc_observe.hpp"
+// target reachability and distance maps of state records (k_reach_rec)
+#include "sparc_reach.hpp"
 
 // step() + the 'new' observation in one launch (SPaRCVecEnv.step): the gym one-call-per-step
 // contract with the planes, the puzzle index and the agent (x | y << 8) of every env
@@ -2429,7 +2431,7 @@ int sparc_sync(void* ctx) {
         if (e & kErrJoin) return fail(c, SPARC_E_STATE, "rule rollout: an audit wave pair did not join (outputs unreliable)");
         if (e & kErrSnapshot)
             return fail(c, SPARC_E_INVALID,
-                        "snapshot / restore / fork / expand / playout / replay / observe / records audit: index or record out "
+                        "snapshot / restore / fork / expand / playout / replay / observe / reach / records audit: index or record out "
                         "of range (those "
                         "envs unchanged, the children of those parents zeroed, the bits and planes of those records 0)");
         return fail(c, SPARC_E_INVALID, "device-side puzzle index out of range in a reset");
@@ -3790,6 +3792,87 @@ int sparc_observe_records_host(void* ctx, const sparc_snapshot_info* info, const
     if (out->puzzle) HIPCHK(c, hipMemcpyAsync(out->puzzle, ds, 4 * m, hipMemcpyDeviceToHost, c->stream));
     if (out->loc) HIPCHK(c, hipMemcpyAsync(out->loc, ds + 4 * m, 8 * m, hipMemcpyDeviceToHost, c->stream));
     if (out->legal) HIPCHK(c, hipMemcpyAsync(out->legal, ds + 12 * m, m, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
+}
+
+// ---- target reachability of records (sparc_reach.hpp): reads the context's tables only
+static int check_reach_args(Ctx* c, const sparc_snapshot_info* info, const void* records, int64_t M,
+                            const sparc_reach_out* out, bool device) {
+    int rc = check_snapshot_info(c, info);
+    if (rc) return rc;
+    if (!records) return fail(c, SPARC_E_INVALID, "null records");
+    if (device && (reinterpret_cast<uintptr_t>(records) & 15u)) return fail(c, SPARC_E_INVALID, "records must be 16-B aligned");
+    if ((rc = check_record_count(c, M, false))) return rc;
+    if (!out) return fail(c, SPARC_E_INVALID, "null out");
+    if (!out->dist && !out->action_dist && !out->live && !out->size && !out->plane)
+        return fail(c, SPARC_E_INVALID, "out: at least one output is needed");
+    if (out->plane) {
+        if (out->x_dim < (int32_t)c->pz.x_max || out->y_dim < (int32_t)c->pz.y_max)
+            return fail(c, SPARC_E_INVALID, "out: x_dim and y_dim must not be below the table's largest x_size and y_size");
+        if ((rc = check_obs_dims(c, out->x_dim, out->y_dim))) return rc;
+    }
+    return SPARC_OK;
+}
+
+// the column masks and the division constant of the flood, from the pitch alone
+static ReachGeom reach_geom(uint32_t pitch, int W) {
+    ReachGeom g{};
+    for (uint32_t b = 0; b < 64u * (uint32_t)W; ++b) {
+        if (b % pitch != 0u) g.nfirst[b >> 6] |= 1ull << (b & 63u);
+        if (b % pitch != pitch - 1u) g.nlast[b >> 6] |= 1ull << (b & 63u);
+    }
+    g.magic = (65536u + pitch - 1u) / pitch;
+    return g;
+}
+
+int sparc_reach_records_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M,
+                               const sparc_reach_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_reach_args(c, info, d_records, M, out, true))) return rc;
+    const Params p = make_params(c);
+    const ReachOut o{out->dist, out->action_dist, out->live, out->size, out->plane,
+                     out->plane ? (uint32_t)out->x_dim : 0u, out->plane ? (uint32_t)out->y_dim : 0u};
+    const ReachGeom g = reach_geom(p.pitch, c->W);
+    const uint4* rec = static_cast<const uint4*>(d_records);
+    const uint32_t m = (uint32_t)M;
+    const size_t lds = (size_t)kSnapBlock * o.XD * o.YD;   // at most 64 KiB
+    dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
+        k_reach_rec<decltype(w)::value, decltype(tb)::value><<<grid_for(m), kSnapBlock, lds, c->stream>>>(p, rec, m, o, g);
+    });
+    return launch_check(c);
+}
+
+int sparc_reach_records_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M,
+                             const sparc_reach_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_reach_args(c, info, records, M, out, false))) return rc;
+    // staged in the expand call's buffers: records | plane | action_dist [M][4], dist, live, size [M]
+    const size_t m = (size_t)M, rbytes = (size_t)info->record_bytes * m;
+    const size_t xy = out->plane ? (size_t)out->x_dim * out->y_dim : 0;
+    HIPCHK(c, c->fk_rec.reserve(rbytes));
+    HIPCHK(c, c->ex_child.reserve(std::max<size_t>(m * xy, 16)));
+    HIPCHK(c, c->ex_out.reserve(7 * m));
+    uint8_t* dp = c->ex_child.get();
+    uint8_t* ds = c->ex_out.get();
+    HIPCHK(c, hipMemcpyAsync(c->fk_rec.get(), records, rbytes, hipMemcpyHostToDevice, c->stream));
+    sparc_reach_out d = *out;
+    d.plane = out->plane ? dp : nullptr;
+    d.action_dist = out->action_dist ? ds : nullptr;
+    d.dist = out->dist ? ds + 4 * m : nullptr;
+    d.live = out->live ? ds + 5 * m : nullptr;
+    d.size = out->size ? ds + 6 * m : nullptr;
+    if ((rc = sparc_reach_records_device(c, info, c->fk_rec.get(), M, &d))) return rc;
+    if (out->plane) HIPCHK(c, hipMemcpyAsync(out->plane, dp, m * xy, hipMemcpyDeviceToHost, c->stream));
+    if (out->action_dist) HIPCHK(c, hipMemcpyAsync(out->action_dist, ds, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    if (out->dist) HIPCHK(c, hipMemcpyAsync(out->dist, ds + 4 * m, m, hipMemcpyDeviceToHost, c->stream));
+    if (out->live) HIPCHK(c, hipMemcpyAsync(out->live, ds + 5 * m, m, hipMemcpyDeviceToHost, c->stream));
+    if (out->size) HIPCHK(c, hipMemcpyAsync(out->size, ds + 6 * m, m, hipMemcpyDeviceToHost, c->stream));
     return sparc_sync(c);
 }
 

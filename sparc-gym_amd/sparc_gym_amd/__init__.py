@@ -9,7 +9,9 @@ from . import puzzles, synthetic  # noqa: F401
 from .puzzles import PuzzleTable, pack_table, process_puzzles  # noqa: F401
 
 __all__ = ["SPaRC_Gym", "SPaRCVecEnv", "Snapshot", "xcd_local_puzzle_index", "process_puzzles", "pack_table",
-           "PuzzleTable", "register"]
+           "PuzzleTable", "register", "REACH_NONE"]
+
+REACH_NONE = 255   # SPaRCVecEnv.reach: no way to the target (SPARC_REACH_NONE)
 
 
 def __getattr__(name):

@@ -100,6 +100,18 @@ class SparcObserveOut(ctypes.Structure):
 
 assert ctypes.sizeof(SparcObserveOut) == 64
 
+# SPARC_REACH_NONE: no way to the target (sparc_reach_records_device's dist and action_dist, its plane's fill)
+REACH_NONE = 255
+
+
+class SparcReachOut(ctypes.Structure):
+    """sparc_reach_out: the outputs of sparc_reach_records_device / _host, each pointer may be NULL."""
+    _fields_ = [("dist", c_void_p), ("action_dist", c_void_p), ("live", c_void_p), ("size", c_void_p),
+                ("plane", c_void_p), ("x_dim", c_int32), ("y_dim", c_int32)]
+
+
+assert ctypes.sizeof(SparcReachOut) == 48
+
 # SPARC_DFS_*: the status of a record's walk after sparc_dfs_device
 DFS_INVALID, DFS_COMPLETE, DFS_BUDGET, DFS_PENDING, DFS_OVERFLOW = range(5)
 # the columns of its counters
@@ -173,6 +185,10 @@ _SIGS = {
                                       ctypes.POINTER(SparcObserveOut)], c_int32),
     "sparc_observe_records_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64,
                                     ctypes.POINTER(SparcObserveOut)], c_int32),
+    "sparc_reach_records_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64,
+                                    ctypes.POINTER(SparcReachOut)], c_int32),
+    "sparc_reach_records_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64,
+                                  ctypes.POINTER(SparcReachOut)], c_int32),
     "sparc_dfs_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, ctypes.c_uint32,
                           c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
     "sparc_dfs_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, ctypes.c_uint32,

@@ -369,6 +369,50 @@ class SparcCore:
         self._check(self.lib.sparc_observe_records_host(self.ctx, ctypes.byref(info), _ptr(rec), M, ctypes.byref(o)))
         return out
 
+    # ---------------------------------------------------------------- target reachability of records
+    def _check_reach(self, M, x_dim, y_dim, plane, outputs):
+        """The argument rules of sparc_reach_records_device that need no device (ValueError)."""
+        if not 1 <= M < 2**31:
+            raise ValueError("M must be in 1..2^31-1")
+        if plane and (x_dim < self.table.x_max or y_dim < self.table.y_max or x_dim * y_dim > 256):
+            raise ValueError(f"x_dim, y_dim must be at least {self.table.x_max}, {self.table.y_max} (the table's "
+                             "largest lattice) with x_dim * y_dim <= 256")
+        if all(x is None for x in outputs):
+            raise ValueError("out: at least one output is needed")
+
+    def reach_records_device(self, info, d_records, M, x_dim=None, y_dim=None, d_dist=None, d_action_dist=None,
+                             d_live=None, d_size=None, d_plane=None):
+        """sparc_reach_records_device: of M records the distance to the target [M], through each
+        action [M][4], the actions that keep the target reachable [M] (bits 0-3), the size of the
+        target's component [M] and the distance plane [M][x_dim][y_dim], all uint8 with REACH_NONE
+        (255) for "no way", each may be None; reads the context's tables only (asynchronous)."""
+        M = int(M)
+        x_dim = self.table.x_max if x_dim is None else int(x_dim)
+        y_dim = self.table.y_max if y_dim is None else int(y_dim)
+        self._check_reach(M, x_dim, y_dim, d_plane is not None, (d_dist, d_action_dist, d_live, d_size, d_plane))
+        out = _lib.SparcReachOut(d_dist, d_action_dist, d_live, d_size, d_plane, x_dim, y_dim)
+        self._check(self.lib.sparc_reach_records_device(self.ctx, ctypes.byref(info), d_records, M, ctypes.byref(out)))
+
+    def reach_records_host(self, info, records, plane=True, x_dim=None, y_dim=None):
+        """Reach of host records [M, record_bytes]: a dict of host uint8 arrays ``dist`` [M],
+        ``action_dist`` [M, 4], ``live`` [M], ``size`` [M] and, with ``plane``, ``plane``
+        [M, x_dim, y_dim] (synchronous)."""
+        rec = np.ascontiguousarray(records, np.uint8)
+        if rec.ndim != 2 or rec.shape[1] != info.record_bytes or len(rec) < 1:
+            raise ValueError(f"records must be [M, {info.record_bytes}] uint8 with M >= 1")
+        M = len(rec)
+        x_dim = self.table.x_max if x_dim is None else int(x_dim)
+        y_dim = self.table.y_max if y_dim is None else int(y_dim)
+        self._check_reach(M, x_dim, y_dim, bool(plane), (True,))
+        out = {"dist": np.empty(M, np.uint8), "action_dist": np.empty((M, 4), np.uint8), "live": np.empty(M, np.uint8),
+               "size": np.empty(M, np.uint8)}
+        if plane:
+            out["plane"] = np.empty((M, x_dim, y_dim), np.uint8)
+        o = _lib.SparcReachOut(_ptr(out["dist"]), _ptr(out["action_dist"]), _ptr(out["live"]), _ptr(out["size"]),
+                               _ptr(out["plane"]) if plane else None, x_dim, y_dim)
+        self._check(self.lib.sparc_reach_records_host(self.ctx, ctypes.byref(info), _ptr(rec), M, ctypes.byref(o)))
+        return out
+
     # ---------------------------------------------------------------- legal-move playouts of records
     def playout_device(self, info, d_records, M, K, L, seed=0, id0=0, flags=0, d_code=None, d_flags=None,
                        d_steps=None, d_first=None, d_end=None, d_return=None, d_trace=None, d_final=None,

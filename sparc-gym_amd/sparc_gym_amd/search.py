@@ -40,17 +40,24 @@ def _done_mask(done, M, device):
     return (d.to(torch.int64) & DONE_BITS) != 0
 
 
-def expand_frontier(vec, snap, done=None):
+def expand_frontier(vec, snap, done=None, prune=False):
     """Expand ``snap`` once and keep only the children that are real moves of a live parent:
     child ``(j, a)`` stays iff bit ``a`` of parent ``j``'s legal mask is set and ``done[j]`` is
     not.  ``done``: [M] bool, or the flag bytes the parents were produced with (bits 0-1:
     terminated, truncated); default: every parent is live.  Returns a dict: ``children`` (a
     ``Snapshot`` of the K kept records, on the GPU), ``parent`` [K] int64 (row of ``snap``),
     ``action`` [K] int64, ``reward_code`` [K] int8, ``flags`` [K] uint8, in ascending
-    ``4 * parent + action``.  ``flags`` are the done bits for the next level."""
+    ``4 * parent + action``.  ``flags`` are the done bits for the next level.
+
+    ``prune=True``: child ``(j, a)`` stays only if bit ``a`` of ``vec.reach(snap)["live"]`` is also
+    set, that is, if the target can still be reached from it over the points the path has left
+    free.  A child that cannot is lost with everything below it; the children that are traceback
+    pops go as well (they lead onto a visited point).  The order of the kept rows is unchanged."""
     out = vec.expand(snap)
     M = len(snap)
     legal = out["legal_mask"].to(torch.int64)
+    if prune:
+        legal = legal & vec.reach(snap)["live"].to(torch.int64)
     keep = ((legal[:, None] >> torch.arange(4, device=legal.device)) & 1) != 0
     if done is not None:
         keep &= ~_done_mask(done, M, legal.device)[:, None]
@@ -466,7 +473,7 @@ def solve_dfs(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, 
     return res
 
 
-def solve_by_rules(vec, puzzle_indices, max_frontier=1 << 22):
+def solve_by_rules(vec, puzzle_indices, max_frontier=1 << 22, prune=False):
     """Every self-avoiding path from the start to the target of each of ``puzzle_indices`` (one
     root per entry: that puzzle's reset state, all roots at once), with the puzzle's own verdict on
     it: the rule audit of the state the path ends in (``vec.audit_records``), beside the verdict of
@@ -489,7 +496,11 @@ def solve_by_rules(vec, puzzle_indices, max_frontier=1 << 22):
     their rule bits, ``satisfied`` [K_r] bool (``bits & RULE_ALL``), ``listed`` [K_r] bool (the last
     step's reward code was +100: the path is in the puzzle's solution list); and ``nodes`` int64
     [R, D + 1], the forward-move nodes at each depth (column 0: the roots).  Nothing asserts that
-    ``satisfied`` and ``listed`` agree: that is a fact about a dataset."""
+    ``satisfied`` and ``listed`` agree: that is a fact about a dataset.
+
+    ``prune=True`` walks with ``expand_frontier(..., prune=True)``: a child from which the target
+    cannot be reached any more has no target node below it, so ``paths``, ``bits``, ``satisfied``
+    and ``listed`` are the same, in the same order, and only ``nodes`` gets smaller."""
     q = np.asarray(puzzle_indices, np.int64)
     R = len(q)
     if q.ndim != 1 or R < 1 or R > vec.num_envs:
@@ -508,7 +519,7 @@ def solve_by_rules(vec, puzzle_indices, max_frontier=1 << 22):
     levels = []                                          # per level: parent, action, live rows
     hits = []                                            # per level: (rows, roots, bits, listed) of its target nodes
     while len(frontier):
-        out = expand_frontier(vec, frontier)             # the frontier holds live nodes only
+        out = expand_frontier(vec, frontier, prune=prune)   # the frontier holds live nodes only
         children, parent, action = out["children"], out["parent"], out["action"]
         code, flags = out["reward_code"], out["flags"]
         if vec.traceback and len(children):              # drop the pops: one point shorter than the parent

@@ -41,6 +41,9 @@ an env; ``roots(puzzle_indices)`` gives reset states as records (``search.score_
 of envs: the ``visited`` and ``agent_location`` planes in the network's dtype, optionally straight
 into two channels of the network's input tensor, with ``puzzle_index``, ``agent_xy`` and
 ``legal_actions``, again in one launch without an env (``search.solution_dataset``).
+``reach(snap, plane)`` tells for records whether the free lattice points still connect the agent to the
+target, the distance to it overall and through each action, and optionally the distance plane, again in
+one launch without an env (``search.expand_frontier(..., prune=True)``).
 """
 from __future__ import annotations
 
@@ -299,7 +302,62 @@ class _RecordObserve:
                 "legal_actions": legal}
 
 
-class SPaRCVecEnv(_RecordReplay, _RecordObserve):
+REACH_NONE = _lib.REACH_NONE
+
+
+class _RecordReach:
+    """``reach`` of ``SPaRCVecEnv``: target reachability and distances of records.  A base class of
+    its own for the reason ``_RecordReplay`` is one; tests/test_reach_guards.py and
+    tests/test_gpu_reach.py check the stream contract for it."""
+
+    def reach(self, snap, plane=False):
+        """Can each record of ``snap`` still reach its puzzle's target, and how far away is it: a
+        flood of the lattice points the path has left free, from the target, in one launch and
+        without changing or reading any env (k_reach_rec).  A path is self-avoiding, so a record
+        the path has walled off from the target is lost whatever the rules say, and so is every
+        record below it.
+
+        Returns a dict of GPU uint8 tensors, ``REACH_NONE`` (255) standing for "no way":
+        ``dist`` [M], 0 on the target, else the moves still needed at least; ``action_dist``
+        [M, 4], the same through each action (exactly ``dist`` of that child of ``expand``, plus
+        1); ``live`` [M], bit a set when action a keeps the target reachable, a subset of the
+        forward legal moves; ``size`` [M], the number of free points connected to the target; with
+        ``plane=True`` also ``plane`` [M, x_dim, y_dim], the distance to the target of every such
+        point and 255 elsewhere (an input channel, or a shaping potential).  Only the puzzle, the
+        agent's point and the visited board of a record enter; a pending record is answered as it
+        stands.
+
+        A record that fails the kernel's checks gets ``dist`` and ``action_dist`` 255, ``live`` 0,
+        ``size`` 0 and a plane of 255, and the next ``core.sync()`` raises.  ValueError: an empty
+        ``snap``, a snapshot header that does not match this env (naming the field)."""
+        from .snapshot import info_mismatch
+        self._stream()
+        M = len(snap)
+        if not 1 <= M < 2**31:
+            raise ValueError("snap must hold 1 .. 2^31 - 1 records")
+        info = self.core.snapshot_info()
+        bad = info_mismatch(snap.info, info)
+        if bad is not None:
+            raise ValueError(f"snapshot does not match this env: {bad} differs")
+        rec = snap.records
+        if not isinstance(rec, torch.Tensor):
+            rec = torch.from_numpy(np.ascontiguousarray(rec, np.uint8))
+        rec = rec.to(self.device).contiguous()
+        dev, X, Y = self.device, self.x_dim, self.y_dim
+        out = {"dist": torch.empty(M, dtype=torch.uint8, device=dev),
+               "action_dist": torch.empty((M, 4), dtype=torch.uint8, device=dev),
+               "live": torch.empty(M, dtype=torch.uint8, device=dev),
+               "size": torch.empty(M, dtype=torch.uint8, device=dev)}
+        if plane:
+            out["plane"] = torch.empty((M, X, Y), dtype=torch.uint8, device=dev)
+        self.core.reach_records_device(snap.info, rec.data_ptr(), M, X, Y, d_dist=out["dist"].data_ptr(),
+                                       d_action_dist=out["action_dist"].data_ptr(), d_live=out["live"].data_ptr(),
+                                       d_size=out["size"].data_ptr(),
+                                       d_plane=out["plane"].data_ptr() if plane else None)
+        return out
+
+
+class SPaRCVecEnv(_RecordReplay, _RecordObserve, _RecordReach):
     def __init__(self, num_envs, puzzles=None, df_name="lkaesberg/SPaRC", df_split="all", df_set="test",
                  observation="new", traceback=False, max_steps=2000, autoreset="next_step", device=0,
                  env_offset=0, pitch=None, words=None, processed=None, table=None, rules=False, copy=True,
