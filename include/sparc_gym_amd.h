@@ -794,6 +794,7 @@ int sparc_set_rule_limits(void *ctx, uint32_t fit_cap_nodes, uint64_t table_entr
  *            word a previous call wrote, and d_records[j] must be that call's cursor:
  *              bits 0-7   the root's path length
  *              bits 8-10  the next action to try at the cursor, 0..4
+ *              bits 12-13 the walk's prune mode (sparc_dfs_pruned_device; this call writes 0)
  *              bit 28     SPARC_DFS_STATE_DONE     nothing is left to walk
  *              bit 29     SPARC_DFS_STATE_FOUND    first_sat[j] has been written
  *              bit 30     SPARC_DFS_STATE_LEAF     the cursor is an entered target leaf whose
@@ -858,6 +859,42 @@ int sparc_dfs_device(void *ctx, const sparc_snapshot_info *info, const void *d_r
  * counts and und_count are read, updated and written back, first_sat is read and written back */
 int sparc_dfs_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
                    uint32_t budget, uint32_t *state, const sparc_dfs_out *out);
+
+/* ---- the pruned depth-first search (additive; SPARC_ABI_VERSION is unchanged) ------------------
+ * sparc_dfs_device with another set of children per node, the root included, and nothing else
+ * changed.  With F, C, D, action_dist and live of a node's state as sparc_reach_records_device
+ * defines them (the agent's own point is visited), the children are
+ *   prune = SPARC_DFS_PRUNE_REACH (1)     the forward moves a with live bit a set: the target can
+ *                                         still be reached through them;
+ *   prune = REACH | SPARC_DFS_PRUNE_DEADLINE (3)  of those, the moves with
+ *                                         node.step + action_dist[a] <= max_steps (computed without
+ *                                         wrapping): the target can still be reached in time;
+ *   prune = 0                             every forward move: the walk of sparc_dfs_device.
+ * Any other value is SPARC_E_INVALID naming the argument, before any launch.  Action order,
+ * pre-order, one real step() per entered child, the leaf classes, the audit of target leaves,
+ * undecided leaves and OVERFLOW, the cursor, first_sat, "k calls of budget B do exactly the first
+ * k * B nodes of the (pruned) pre-order walk" and the byte-for-byte promise for every record written
+ * are those of sparc_dfs_device.  A live root with no admissible child is one dead end, COMPLETE,
+ * with no node entered (a start walled off from its target, or one the limit cuts off from it).
+ * Consequences, for the same root and max_steps (facts, not choices; the tests pin them):
+ *   TARGETS, SATISFIED, LISTED, BOTH, UNDECIDED and first_sat equal the unpruned walk's;
+ *   DEAD_ENDS is 0 below the root under REACH (an entered non-target node always has a live move);
+ *   TRUNCATED is 0 under DEADLINE.
+ * With both cuts every entered node lies on a path that reaches the target in time.
+ * The state word records the mode of its walk in bits 12-13 (zero in every word sparc_dfs_device
+ * writes, so those words are valid prune = 0 words here).  A state word that is neither 0 nor DONE
+ * and whose mode differs from `prune` is refused on the device like a cursor above its root: status
+ * SPARC_DFS_INVALID, d_state[j] becomes DONE, sparc_sync reports the error, every other record is
+ * unaffected.  sparc_dfs_device itself does not read those bits.
+ * Needs what sparc_dfs_device needs; the flood's column masks come from the pitch alone, as for
+ * sparc_reach_records_device. */
+#define SPARC_DFS_PRUNE_REACH 1
+#define SPARC_DFS_PRUNE_DEADLINE 2
+#define SPARC_DFS_STATE_MODE_SHIFT 12
+int sparc_dfs_pruned_device(void *ctx, const sparc_snapshot_info *info, const void *d_records, int64_t M,
+                            uint32_t budget, int32_t prune, uint32_t *d_state, const sparc_dfs_out *out);
+int sparc_dfs_pruned_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
+                          uint32_t budget, int32_t prune, uint32_t *state, const sparc_dfs_out *out);
 
 /* ---- debug: kernel variants (A/B runs and tests) ----------------------------------------------
  * Selects, for this context, among kernel variants that compute identical results.  Callers never

@@ -56,6 +56,8 @@ enum : uint32_t { kDfsNodes = 0, kDfsTargets, kDfsSatisfied, kDfsListed, kDfsBot
 // the state word: root path length | next action << 8 | flags
 constexpr uint32_t kDfsNextShift = 8, kDfsDone = 1u << 28, kDfsFound = 1u << 29, kDfsLeaf = 1u << 30,
                    kDfsStarted = 1u << 31;
+constexpr uint32_t kDfsModeShift = 12;   // bits 12-13: the walk's prune mode (0: every forward move)
+constexpr uint32_t kDfsPruneReach = 1, kDfsPruneDeadline = 2;   // SPARC_DFS_PRUNE_*
 constexpr uint32_t kRuleAllBit = 1u << 8, kRuleExhaustedBit = 1u << 9;   // SPARC_RULE_ALL, _SEARCH_EXHAUSTED
 
 struct DfsOut {
@@ -68,6 +70,13 @@ struct DfsOut {
     unsigned long long* __restrict__ und_count;
     uint64_t und_cap;
 };
+
+// the prune mode of a children policy (0 where it has none)
+template <class Moves>
+__device__ __forceinline__ uint32_t dfs_mode(const Moves& mv) {
+    if constexpr (Moves::kPrune) return mv.mode;
+    else return 0u;
+}
 
 // the forward moves of the state: its legal actions without the traceback pop
 template <int W>
@@ -156,10 +165,20 @@ __device__ __forceinline__ void dfs_slot_record(const State& s, uint32_t t, uint
     }
 }
 
-// Record j < M (M < 2^31): see the head of this file and sparc_dfs_device (sparc_gym_amd.h).
-template <int W, bool TABLE_ONLY>
+// Which children a node of the walk has: every forward move (the search of sparc_dfs_device; with this
+// policy k_dfs compiles to what it was without one).  The pruned walk's policy (DfsLiveMoves,
+// sparc_dfs_prune.hpp) has kPrune set, a `mode` and a wave-collective moves<W>(e, p, ask); the lines
+// under `Moves::kPrune` below are that walk's and are described there.
+struct DfsAllMoves {
+    static constexpr bool kPrune = false;
+};
+
+// Record j < M (M < 2^31): see the head of this file and sparc_dfs_device (sparc_gym_amd.h).  `mv`: the
+// children policy, DfsAllMoves (an empty argument) for the search of sparc_dfs_device.
+template <int W, bool TABLE_ONLY, class Moves = DfsAllMoves>
 __global__ void __launch_bounds__(kSnapBlock) k_dfs(Params p, RulesTab rt, const uint4* rec, uint32_t M,
-                                                    uint32_t budget, uint32_t* __restrict__ state, DfsOut o) {
+                                                    uint32_t budget, uint32_t* __restrict__ state, DfsOut o,
+                                                    Moves mv) {
     static_assert(!TABLE_ONLY || W == 1, "the table-only audit is the one-word one");
     using R = SnapRec<W, true>;
     constexpr int kD = 2 * W;
@@ -205,6 +224,8 @@ __global__ void __launch_bounds__(kSnapBlock) k_dfs(Params p, RulesTab rt, const
             atomicOr(p.err, (int)kErrRuleTable);
         } else if (st0 != 0u && ((st0 & 0xFFu) < 1u || (st0 & 0xFFu) > len)) {
             atomicOr(p.err, (int)kErrSnapshot);   // a cursor above its own root
+        } else if (Moves::kPrune && st0 != 0u && ((st0 >> kDfsModeShift) & 3u) != dfs_mode(mv)) {
+            atomicOr(p.err, (int)kErrSnapshot);   // a cursor of a walk of another mode
         } else {
             ok = true;
 #pragma unroll
@@ -236,6 +257,10 @@ __global__ void __launch_bounds__(kSnapBlock) k_dfs(Params p, RulesTab rt, const
     uint32_t status = was_done ? kDfsComplete : kDfsInvalid;
     uint32_t root_len = 0, next = 0;
     bool live = false, found = false, owe = false;
+    // the pruned walk: the moves of the node the lane stands on (valid unless `need`), and whether
+    // that node still owes its dead-end test (the root, or a node entered on the trip before)
+    uint32_t moves = 0;
+    bool need = true, fresh = false;
     uint32_t cnt[kDfsCounters];
 #pragma unroll
     for (int k = 0; k < (int)kDfsCounters; ++k) cnt[k] = 0;
@@ -244,6 +269,9 @@ __global__ void __launch_bounds__(kSnapBlock) k_dfs(Params p, RulesTab rt, const
             root_len = e.len;
             if (e.pending) {
                 status = kDfsPending;
+            } else if constexpr (Moves::kPrune) {
+                live = true;                                  // its moves are asked for in the loop
+                fresh = true;
             } else if (dfs_children<W>(e) == 0u) {
                 cnt[kDfsDeadEnds] = 1;
                 status = kDfsComplete;
@@ -263,12 +291,28 @@ __global__ void __launch_bounds__(kSnapBlock) k_dfs(Params p, RulesTab rt, const
     const uint64_t trips = 2ull * budget + 600ull;
     for (uint64_t it = 0; it < trips; ++it) {
         if (__ballot(live) == 0ull) break;
+        if constexpr (Moves::kPrune) {
+            // Every lane of the wave takes part (the flood leaves on a ballot); a lane with nothing
+            // to ask passes an empty board.  The loop itself is left on a ballot only.
+            const bool ask = live && !owe && need && !e.pending;
+            if (__ballot(ask) != 0ull) {
+                const uint32_t m = mv.template moves<W>(e, p, ask);
+                if (ask) {
+                    moves = m;
+                    need = false;
+                    if (fresh && m == 0u) cnt[kDfsDeadEnds] += 1u;
+                    fresh = false;
+                }
+            }
+        }
         bool tgt = false;
         if (live) {
             if (owe) {
                 tgt = true;                                   // the leaf an overflow left unaccounted
             } else {
-                const uint32_t cand = e.pending ? 0u : (dfs_children<W>(e) >> next) << next;
+                uint32_t cand;
+                if constexpr (Moves::kPrune) cand = e.pending ? 0u : (moves >> next) << next;
+                else cand = e.pending ? 0u : (dfs_children<W>(e) >> next) << next;
                 if (cand != 0u) {
                     if (ahead) {
                         live = false;                         // more to walk: the stored cursor stands
@@ -281,7 +325,9 @@ __global__ void __launch_bounds__(kSnapBlock) k_dfs(Params p, RulesTab rt, const
                         cnt[kDfsNodes] += 1u;
                         if (f & 1u) tgt = true;
                         else if (f & 2u) cnt[kDfsTruncated] += 1u;
+                        else if constexpr (Moves::kPrune) fresh = true;   // its dead-end test: the next trip
                         else if (dfs_children<W>(e) == 0u) cnt[kDfsDeadEnds] += 1u;
+                        need = true;
                     }
                 } else if (e.len <= root_len) {
                     live = false;
@@ -290,6 +336,7 @@ __global__ void __launch_bounds__(kSnapBlock) k_dfs(Params p, RulesTab rt, const
                     const uint32_t a = dfs_last_move<W>(e);
                     dfs_undo(e, q);
                     next = a + 1u;
+                    need = true;                              // the parent's moves: one flood per trip
                 }
             }
         }
@@ -387,6 +434,7 @@ __global__ void __launch_bounds__(kSnapBlock) k_dfs(Params p, RulesTab rt, const
                 const uint32_t nx = status == kDfsBudget && !ahead ? next : 0u;   // a stored cursor is a fresh node
                 stw = kDfsStarted | root_len | (nx << kDfsNextShift) | (done ? kDfsDone : 0u) |
                       (found ? kDfsFound : 0u) | (owe ? kDfsLeaf : 0u);
+                if constexpr (Moves::kPrune) stw |= dfs_mode(mv) << kDfsModeShift;
             }
             state[j] = stw;
 #pragma unroll

@@ -13,6 +13,7 @@
 //   k_playout  K legal-move playouts of each state record, without an env (sparc_playout.hpp)
 //   k_replay   given action sequences played from records or puzzle roots, without an env (sparc_replay.hpp)
 //   k_dfs      depth-first subtree search of state records with rule verdicts (sparc_dfs.hpp)
+//              and, as k_dfs<.., DfsLiveMoves>, over the moves that can still reach the target (sparc_dfs_prune.hpp)
 // No MFMA: this is integer / bitboard work, bound by latency and HBM.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -482,6 +483,8 @@ __device__ __forceinline__ void obs_write_stream(ObsStream<W>* os, uint32_t lane
 #include "sparc_observe.hpp"
 // target reachability and distance maps of state records (k_reach_rec)
 #include "sparc_reach.hpp"
+// the pruned depth-first search of state records (k_dfs_pruned): the walk of sparc_dfs.hpp on the flood
+#include "sparc_dfs_prune.hpp"
 
 // step() + the 'new' observation in one launch (SPaRCVecEnv.step): the gym one-call-per-step
 // contract with the planes, the puzzle index and the agent (x | y << 8) of every env
@@ -4110,13 +4113,20 @@ static int check_dfs_args(Ctx* c, const sparc_snapshot_info* info, const void* r
     return SPARC_OK;
 }
 
-int sparc_dfs_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M, uint32_t budget,
-                     uint32_t* d_state, const sparc_dfs_out* out) {
-    DevGuard dg;
-    Ctx* c = static_cast<Ctx*>(ctx);
-    int rc = check_ctx(c, false);
+// prune: 0, SPARC_DFS_PRUNE_REACH or REACH | DEADLINE
+static int check_dfs_prune(Ctx* c, int32_t prune) {
+    if (prune != 0 && prune != SPARC_DFS_PRUNE_REACH && prune != (SPARC_DFS_PRUNE_REACH | SPARC_DFS_PRUNE_DEADLINE))
+        return fail(c, SPARC_E_INVALID, "prune must be 0, SPARC_DFS_PRUNE_REACH (1) or REACH | DEADLINE (3)");
+    return SPARC_OK;
+}
+
+// mode_check: refuse the cursors of pruned walks first (k_dfs_mode0); sparc_dfs_device itself reads
+// bits 12-13 of a state word as little as it ever did
+static int dfs_launch(Ctx* c, const sparc_snapshot_info* info, const void* d_records, int64_t M, uint32_t budget,
+                      int32_t prune, bool mode_check, uint32_t* d_state, const sparc_dfs_out* out) {
+    int rc = check_dfs_args(c, info, d_records, M, budget, d_state, out, true);
     if (rc) return rc;
-    if ((rc = check_dfs_args(c, info, d_records, M, budget, d_state, out, true))) return rc;
+    if ((rc = check_dfs_prune(c, prune))) return rc;
     const Params p = make_params(c);
     const RulesTab rt = rules_tab(c, c->rl, false);   // no exact-fit queue: such leaves are undecided
     const DfsOut o{out->status,
@@ -4130,7 +4140,19 @@ int sparc_dfs_device(void* ctx, const sparc_snapshot_info* info, const void* d_r
     const uint4* rec = static_cast<const uint4*>(d_records);
     const uint32_t m = (uint32_t)M;
     const dim3 gr((unsigned)(((uint64_t)M + kSnapBlock - 1) / kSnapBlock));
-    auto go = [&](auto kern) { kern<<<gr, kSnapBlock, 0, c->stream>>>(p, rt, rec, m, budget, d_state, o); };
+    if (prune != 0) {
+        const DfsLiveMoves mv{reach_geom(p.pitch, c->W), (uint32_t)prune};
+        auto go = [&](auto kern) { kern<<<gr, kSnapBlock, 0, c->stream>>>(p, rt, rec, m, budget, d_state, o, mv); };
+        if (c->W == 1 && c->rl.tab_all) go(k_dfs<1, true, DfsLiveMoves>);
+        else if (c->W == 1) go(k_dfs<1, false, DfsLiveMoves>);
+        else if (c->W == 2) go(k_dfs<2, false, DfsLiveMoves>);
+        else go(k_dfs<4, false, DfsLiveMoves>);
+        return launch_check(c);
+    }
+    if (mode_check) k_dfs_mode0<<<gr, kSnapBlock, 0, c->stream>>>(d_state, m);
+    auto go = [&](auto kern) {
+        kern<<<gr, kSnapBlock, 0, c->stream>>>(p, rt, rec, m, budget, d_state, o, DfsAllMoves{});
+    };
     // the table-only audit when every puzzle has a region-code table, as launch_rules chooses it
     if (c->W == 1 && c->rl.tab_all) go(k_dfs<1, true>);
     else if (c->W == 1) go(k_dfs<1, false>);
@@ -4139,13 +4161,29 @@ int sparc_dfs_device(void* ctx, const sparc_snapshot_info* info, const void* d_r
     return launch_check(c);
 }
 
-int sparc_dfs_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M, uint32_t budget,
-                   uint32_t* state, const sparc_dfs_out* out) {
+int sparc_dfs_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M, uint32_t budget,
+                     uint32_t* d_state, const sparc_dfs_out* out) {
     DevGuard dg;
     Ctx* c = static_cast<Ctx*>(ctx);
     int rc = check_ctx(c, false);
     if (rc) return rc;
-    if ((rc = check_dfs_args(c, info, records, M, budget, state, out, false))) return rc;
+    return dfs_launch(c, info, d_records, M, budget, 0, false, d_state, out);
+}
+
+int sparc_dfs_pruned_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M,
+                            uint32_t budget, int32_t prune, uint32_t* d_state, const sparc_dfs_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    return dfs_launch(c, info, d_records, M, budget, prune, true, d_state, out);
+}
+
+static int dfs_host(Ctx* c, const sparc_snapshot_info* info, const void* records, int64_t M, uint32_t budget,
+                    int32_t prune, bool mode_check, uint32_t* state, const sparc_dfs_out* out) {
+    int rc = check_dfs_args(c, info, records, M, budget, state, out, false);
+    if (rc) return rc;
+    if ((rc = check_dfs_prune(c, prune))) return rc;
     const size_t m = (size_t)M, rb = (size_t)info->record_bytes, bytes = rb * m;
     const size_t cap = out->und_rec ? (size_t)out->und_cap : 0;
     // u64 words: counts [8m] | und_count | then state [m] u32, und_root [cap] u32, status [m] u8
@@ -4171,7 +4209,7 @@ int sparc_dfs_host(void* ctx, const sparc_snapshot_info* info, const void* recor
     HIPCHK(c, hipMemcpyAsync(d_state, state, 4 * m, hipMemcpyHostToDevice, c->stream));
     if (d.und_count) HIPCHK(c, hipMemcpyAsync(d.und_count, out->und_count, 8, hipMemcpyHostToDevice, c->stream));
     if (d.first_sat) HIPCHK(c, hipMemcpyAsync(d.first_sat, out->first_sat, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = sparc_dfs_device(c, info, c->fk_rec.get(), M, budget, d_state, &d))) return rc;
+    if ((rc = dfs_launch(c, info, c->fk_rec.get(), M, budget, prune, mode_check, d_state, &d))) return rc;
     HIPCHK(c, hipMemcpyAsync(out->status, d.status, m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out->counts, d.counts, 64 * m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(state, d_state, 4 * m, hipMemcpyDeviceToHost, c->stream));
@@ -4191,6 +4229,24 @@ int sparc_dfs_host(void* ctx, const sparc_snapshot_info* info, const void* recor
         }
     }
     return sparc_sync(c);
+}
+
+int sparc_dfs_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M, uint32_t budget,
+                   uint32_t* state, const sparc_dfs_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    return dfs_host(c, info, records, M, budget, 0, false, state, out);
+}
+
+int sparc_dfs_pruned_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M, uint32_t budget,
+                          int32_t prune, uint32_t* state, const sparc_dfs_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    return dfs_host(c, info, records, M, budget, prune, true, state, out);
 }
 
 // ---- rule audit of records (sparc_rules_rec.hpp): reads the context's tables only

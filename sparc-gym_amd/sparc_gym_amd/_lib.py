@@ -120,6 +120,21 @@ DFS_INVALID, DFS_COMPLETE, DFS_BUDGET, DFS_PENDING, DFS_OVERFLOW = range(5)
 DFS_COUNTER_NAMES = ("nodes", "targets", "satisfied", "listed", "both", "dead_ends", "truncated", "undecided")
 # SPARC_DFS_STATE_*: bits of the state word (bits 0-7: the root's path length, 8-10: the next action)
 DFS_STATE_DONE, DFS_STATE_FOUND, DFS_STATE_LEAF, DFS_STATE_STARTED = 1 << 28, 1 << 29, 1 << 30, 1 << 31
+# SPARC_DFS_PRUNE_*: the children of a node of sparc_dfs_pruned_device (0: every forward move); the
+# state word keeps the mode of its walk in bits 12-13
+DFS_PRUNE_REACH, DFS_PRUNE_DEADLINE, DFS_STATE_MODE_SHIFT = 1, 2, 12
+
+
+def dfs_prune_mode(prune):
+    """The ``prune`` argument of ``dfs`` as the C value: False -> 0, True or "reach" -> 1 (only moves
+    through which the target can still be reached), "deadline" -> 3 (and reached before max_steps)."""
+    if prune is False:
+        return 0
+    if prune is True or prune == "reach":
+        return DFS_PRUNE_REACH
+    if prune == "deadline":
+        return DFS_PRUNE_REACH | DFS_PRUNE_DEADLINE
+    raise ValueError(f'prune must be False, True, "reach" or "deadline", not {prune!r}')
 
 
 class SparcDfsOut(ctypes.Structure):
@@ -193,6 +208,10 @@ _SIGS = {
                           c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
     "sparc_dfs_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, ctypes.c_uint32,
                         c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
+    "sparc_dfs_pruned_device": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64,
+                                 ctypes.c_uint32, c_int32, c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
+    "sparc_dfs_pruned_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64,
+                               ctypes.c_uint32, c_int32, c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
     "sparc_load_rules": ([c_void_p, ctypes.POINTER(SparcRulesTable)], c_int32),
     "sparc_rules_device": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_rules_host": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),

@@ -529,26 +529,33 @@ class SparcCore:
 
     # ---------------------------------------------------------------- depth-first subtree search of records
     def dfs_device(self, info, d_records, M, budget, d_state, d_status, d_counts, d_cursor, d_first=None,
-                   d_und_rec=None, d_und_root=None, d_und_count=None, und_cap=0):
+                   d_und_rec=None, d_und_root=None, d_und_count=None, und_cap=0, prune=None):
         """sparc_dfs_device: the forward-move subtree below each of M records, walked depth-first
         for at most ``budget`` nodes each, with the rule verdict of every target leaf; state [M]
         uint32 in/out, status [M] uint8, counts [M][8] uint64 accumulated, cursor [M] records,
         optionally first [M] records and the undecided leaves' buffer (all three pointers or none);
-        reads the context's tables only (asynchronous)."""
+        reads the context's tables only (asynchronous).  With ``prune`` (the C value: 0, 1 =
+        ``_lib.DFS_PRUNE_REACH`` or 3 = REACH | DEADLINE) sparc_dfs_pruned_device, which also holds a
+        state word to the mode of its walk; None: sparc_dfs_device itself."""
         M, budget = int(M), int(budget)
         if not 1 <= budget < 2**32:
             raise ValueError("budget must be in 1..2^32-1")
         out = _lib.SparcDfsOut(d_status, d_counts, d_cursor, d_first, d_und_rec, d_und_root, d_und_count, int(und_cap))
-        self._check(self.lib.sparc_dfs_device(self.ctx, ctypes.byref(info), d_records, M, budget, d_state,
-                                              ctypes.byref(out)))
+        if prune is None:
+            self._check(self.lib.sparc_dfs_device(self.ctx, ctypes.byref(info), d_records, M, budget, d_state,
+                                                  ctypes.byref(out)))
+        else:
+            self._check(self.lib.sparc_dfs_pruned_device(self.ctx, ctypes.byref(info), d_records, M, budget,
+                                                         int(prune), d_state, ctypes.byref(out)))
 
-    def dfs_host(self, info, records, budget, state=None, counts=None, first=None, undecided=0):
+    def dfs_host(self, info, records, budget, state=None, counts=None, first=None, undecided=0, prune=None):
         """Walk host records [M, record_bytes] (synchronous): a dict of host arrays ``status`` [M]
         uint8, ``counts`` [M, 8] uint64, ``cursor`` and ``first`` [M, record_bytes] uint8, ``state``
         [M] uint32 and, with ``undecided`` > 0 (the buffer's entries), ``undecided``
         [n, record_bytes] uint8, ``undecided_root`` [n] uint32 and ``undecided_total``.  ``state``,
         ``counts`` and ``first`` of a previous call are continued in place (``records`` is then that
-        call's ``cursor``); fresh zeroed arrays otherwise."""
+        call's ``cursor``); fresh zeroed arrays otherwise.  ``prune``: as ``dfs_device``
+        (sparc_dfs_pruned_host unless None)."""
         rec = np.ascontiguousarray(records, np.uint8)
         if rec.ndim != 2 or rec.shape[1] != info.record_bytes or len(rec) < 1:
             raise ValueError(f"records must be [M, {info.record_bytes}] uint8 with M >= 1")
@@ -575,8 +582,12 @@ class SparcCore:
         count = np.zeros(1, np.uint64) if cap else None
         o = _lib.SparcDfsOut(_ptr(out["status"]), _ptr(counts), _ptr(out["cursor"]), _ptr(first), _ptr(und),
                              _ptr(root), _ptr(count), cap)
-        self._check(self.lib.sparc_dfs_host(self.ctx, ctypes.byref(info), _ptr(rec), M, budget, _ptr(state),
-                                            ctypes.byref(o)))
+        if prune is None:
+            self._check(self.lib.sparc_dfs_host(self.ctx, ctypes.byref(info), _ptr(rec), M, budget, _ptr(state),
+                                                ctypes.byref(o)))
+        else:
+            self._check(self.lib.sparc_dfs_pruned_host(self.ctx, ctypes.byref(info), _ptr(rec), M, budget,
+                                                       int(prune), _ptr(state), ctypes.byref(o)))
         if cap:
             n = min(int(count[0]), cap)
             out.update(undecided=und[:n], undecided_root=root[:n], undecided_total=int(count[0]))

@@ -363,6 +363,8 @@ def solve_dfs(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, 
     which finishes them on the host, and their verdicts added.  ``undecided=0``: such leaves stay
     in the ``undecided`` counter.
 
+    ``solve_dfs_pruned`` is the same search over the moves that can still reach the target.
+
     Needs a traceback env with ``max_steps`` at least the lattice's points (ValueError), at least
     ``len(puzzle_indices)`` envs, and overwrites the env state (the roots come from ``vec.reset``).
 
@@ -372,6 +374,27 @@ def solve_dfs(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, 
     lexicographically least satisfying action list from the puzzle's start found so far, or None
     (final when ``complete``), ``launches``: the ``vec.dfs`` calls made, and ``sub_roots``: the
     frontier the search started from."""
+    return _solve_dfs(vec, puzzle_indices, min_roots, budget, max_nodes, undecided, 0)
+
+
+def solve_dfs_pruned(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, undecided=65536, prune=True):
+    """``solve_dfs`` over the moves through which the target can still be reached: the split uses
+    ``expand_frontier(..., prune=True)`` and the search ``vec.dfs(..., prune=True)``.  Arguments and
+    result as ``solve_dfs``; ``prune``: True or "reach" (False: ``solve_dfs`` itself).  The counters
+    are those of the pruned walk from each puzzle's start: ``solution`` and ``targets``,
+    ``satisfied``, ``listed``, ``both``, ``undecided`` equal ``solve_dfs``'s, ``nodes`` is smaller,
+    and ``dead_ends`` is 1 for a start that is walled off from its target and 0 otherwise (a node the
+    split cuts is not a dead end, it is never entered).  ``max_steps`` is at least the lattice's
+    points here, so the deadline mode of ``vec.dfs`` would cut nothing more (ValueError)."""
+    from . import _lib
+    mode = _lib.dfs_prune_mode(prune)
+    if mode not in (0, _lib.DFS_PRUNE_REACH):
+        raise ValueError('solve_dfs_pruned prunes by reach only: prune must be False, True or "reach"')
+    return _solve_dfs(vec, puzzle_indices, min_roots, budget, max_nodes, undecided, mode)
+
+
+def _solve_dfs(vec, puzzle_indices, min_roots, budget, max_nodes, undecided, mode):
+    """solve_dfs (mode 0) and solve_dfs_pruned (mode 1, _lib.DFS_PRUNE_REACH)."""
     from . import _lib
     q = np.asarray(puzzle_indices, np.int64)
     R = len(q)
@@ -413,7 +436,7 @@ def solve_dfs(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, 
 
     # ---- split: forward-only breadth-first levels
     while 0 < len(frontier) < min_roots:
-        out = expand_frontier(vec, frontier)              # the frontier holds live nodes only
+        out = expand_frontier(vec, frontier, prune=mode != 0)   # the frontier holds live nodes only
         children, parent = out["children"], out["parent"]
         code, flags = out["reward_code"], out["flags"]
         if len(children):                                 # drop the pops: one point shorter than the parent
@@ -421,7 +444,7 @@ def solve_dfs(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, 
             keep = fwd.nonzero().squeeze(1)
             children, parent, code, flags = children.select(keep), parent[keep], code[keep], flags[keep]
         kids = torch.bincount(parent, minlength=len(frontier))
-        add(_lib.DFS_DEAD_ENDS, root[kids == 0])          # live without a forward move
+        add(_lib.DFS_DEAD_ENDS, root[kids == 0])          # live without a forward move (pruned: a start only)
         if len(children) == 0:
             frontier = children
             root = root[:0]
@@ -448,7 +471,8 @@ def solve_dfs(vec, puzzle_indices, min_roots=4096, budget=4096, max_nodes=None, 
         resolved = torch.zeros(M, dtype=torch.int64, device=dev)
         split_nodes = int(total[:, _lib.DFS_NODES].sum())
         while True:
-            out = vec.dfs(cur, budget, state=state, counts=counts, first=first, undecided=undecided)
+            out = vec.dfs(cur, budget, state=state, counts=counts, first=first, undecided=undecided,
+                          prune=mode != 0)
             launches += 1
             cur, state, counts, first = out["cursor"], out["state"], out["counts"], out["first"]
             if undecided and len(out["undecided"]):

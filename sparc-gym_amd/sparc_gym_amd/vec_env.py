@@ -914,7 +914,7 @@ class SPaRCVecEnv(_RecordReplay, _RecordObserve, _RecordReach):
         self.core.rules_finish(out["bits"].data_ptr(), d_fit)   # rec lives until here: the re-run reads it
         return out
 
-    def dfs(self, snap, budget, state=None, counts=None, first=None, undecided=0):
+    def dfs(self, snap, budget, state=None, counts=None, first=None, undecided=0, prune=False):
         """Depth-first search of the forward-move subtree below every record of ``snap`` (M of
         them), at most ``budget`` entered nodes per record and call, in one launch and without
         changing or reading any env (k_dfs).  A node's children are its legal actions without the
@@ -938,8 +938,20 @@ class SPaRCVecEnv(_RecordReplay, _RecordObserve, _RecordReach):
         (Snapshot of the n stored ones), ``undecided_root`` [n] int64 (their rows of ``snap``) and
         ``undecided_total`` int; a walk whose leaf did not fit stops with status 4 and resumes at
         that leaf.  A record that fails the kernel's checks gets status 0 and a zeroed cursor, and
-        the next ``core.sync()`` raises."""
+        the next ``core.sync()`` raises.
+
+        ``prune`` cuts the tree without losing a target leaf.  True or "reach": a node's children are
+        only the forward moves through which the free lattice points still connect to the target
+        (the ``live`` bits of ``reach`` for that node).  "deadline": of those, only the moves from
+        which the target is still reached by ``max_steps`` (step + ``action_dist`` <= max_steps).
+        Everything else is the unpruned walk: ``targets``, ``satisfied``, ``listed``, ``both``,
+        ``undecided`` and ``first`` are equal, ``nodes`` is smaller, ``dead_ends`` is 0 below the
+        root (a root cut off from its target is one dead end) and, under "deadline", ``truncated``
+        is 0.  Continue a walk with the ``prune`` it began with: the state word records it, and a
+        cursor of another mode is refused like a bad record (status 0).  Any other value raises
+        ValueError."""
         from .snapshot import Snapshot, info_mismatch
+        mode = _lib.dfs_prune_mode(prune)
         self._stream()
         if not self.traceback:
             raise ValueError("dfs needs a traceback env: the record's direction stack is the search stack")
@@ -983,7 +995,7 @@ class SPaRCVecEnv(_RecordReplay, _RecordObserve, _RecordReach):
         self.core.dfs_device(snap.info, rec.data_ptr(), M, budget, state.data_ptr(), status.data_ptr(),
                              counts.data_ptr(), cursor.data_ptr(), first.data_ptr(),
                              und.data_ptr() if cap else None, root.data_ptr() if cap else None,
-                             count.data_ptr() if cap else None, cap)
+                             count.data_ptr() if cap else None, cap, prune=mode)
         out = {"status": status, "counts": counts, "cursor": Snapshot(cursor, snap.info), "state": state,
                "first": Snapshot(first, snap.info), "found": (state & _lib.DFS_STATE_FOUND) != 0,
                "done": (state & _lib.DFS_STATE_DONE) != 0}
