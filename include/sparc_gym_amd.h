@@ -896,6 +896,86 @@ int sparc_dfs_pruned_device(void *ctx, const sparc_snapshot_info *info, const vo
 int sparc_dfs_pruned_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
                           uint32_t budget, int32_t prune, uint32_t *state, const sparc_dfs_out *out);
 
+/* ---- UCT tree search of records with resumable trees (additive; SPARC_ABI_VERSION is unchanged) --
+ * One search tree per record, grown by `sims` simulations per call in one launch and without
+ * touching an env: as with sparc_playout_device the context supplies its puzzle table, words, pitch,
+ * traceback and max_steps only, its env state is neither read nor written, and sparc_load_puzzles
+ * is enough.  The reference has no counterpart; the moves are its own: the children of a node are
+ * its legal actions (_get_legal_actions, SPaRC_Gym.py:1024-1051) without the traceback pop
+ * (1141-1166), the "forward moves" of sparc_dfs_device, on a context without traceback all legal
+ * actions, whatever `flags` says, and every edge is one step() (1111-1238).
+ * The tree of root j is d_nodes[j][0 .. d_count[j]) of a caller-owned arena [M][cap] of 64-byte
+ * nodes (16 uint32, the arena 64-B aligned), node 0 the root; d_count[j] = 0 is a fresh tree (the
+ * call writes node 0).  A node:
+ *   w0       bits 0-27 the parent's index, bits 28-29 the action that entered the node, bits 30-31
+ *            its kind, fixed when it is created from the step that entered it: 1 the step
+ *            terminated, 2 it truncated, else 3 when the state has no forward move (a dead end)
+ *            and 0 (inner) when it has
+ *   w1-w3    visits, wins (simulations through the node whose last reward code was +100), losses
+ *            (-100)
+ *   w4-w7    child[a]: 0 not yet tried (no child is node 0), 0xFFFFFFFF not a child (every action of
+ *            a node of kind != 0), else the child's index
+ *   w8-w11   n[a], the visits of that child;  w12-w15  wins[a], its wins
+ * Simulation s of root j, s being the root's visits before it (so s counts across calls), starts at
+ * node 0 in the root's state.  At an inner node with an untried child it takes the lowest untried
+ * action, steps, appends the new node at index d_count[j]++ and, if that node is inner, rolls out
+ * from it: sparc_playout_device's loop for t = 0 .. L-1 with
+ * a = sparc_rand_pick(seed, id0 + j * 2^32 + s, t, mask), SPARC_PLAYOUT_FORWARD clearing the pop
+ * from the mask on a traceback context, ended by the step that ends the episode or by a dead end.
+ * At an inner node with every child tried it takes the first action, in action order under strict
+ * >, that maximises wins[a] / n[a] + d_ep[min(visits, T-1)] * d_ec[min(n[a], T-1)], computed in
+ * float32 with each of the three operations (and the two integer conversions) rounded to nearest on
+ * its own, steps, and goes on from that child; entering a node of kind != 0 ends the simulation.
+ * Its outcome is the reward code of its last step, in the tree or in the rollout; the backup walks
+ * the parent links from the deepest tree node to the root: visits + 1 and wins / losses by the
+ * outcome on each node, n[a] and wins[a] of the edge taken on each parent.
+ * out->status[j] (uint8) and out->sims_done[j] (uint32, the simulations of this call):
+ *   SPARC_MCTS_DONE      `sims` simulations were made
+ *   SPARC_MCTS_FULL      the next simulation needed a node with d_count[j] == cap, or the root's
+ *                        visits are 0xFFFFFFFF: it was not started and nothing of it is counted, so
+ *                        the call can be repeated on a larger arena
+ *   SPARC_MCTS_PENDING   the record's last step ended its episode; the arena is not touched
+ *   SPARC_MCTS_DEAD_END  the record is live without a forward move; the arena is not touched
+ *   SPARC_MCTS_INVALID   the record fails the checks of sparc_restore_device, d_count[j] > cap, or a
+ *                        simulation met a child index outside (its node, d_count[j]) or a child whose
+ *                        parent index and action do not point back: sparc_sync reports the error,
+ *                        every other root is unaffected, and no byte outside nodes[j][0 .. cap) is
+ *                        read or written for root j.
+ * k calls of S simulations leave the arena, d_count, win_rec and win_steps byte for byte as one call
+ * of k * S does.  out->win_rec [M] records (16-B aligned) and out->win_steps [M] uint32 are in/out
+ * (the caller sets win_steps to 0xFFFFFFFF first): a simulation whose outcome is +100 and whose
+ * steps from the root are fewer than win_steps[j] replaces both; the record is byte for byte what
+ * sparc_restore_device of record j, those steps and sparc_snapshot_device give.
+ * d_ep, d_ec: two float32 tables of T >= 2 entries (no transcendental function runs on the device).
+ * SPARC_E_INVALID naming the argument, before any launch, unless 1 <= M < 2^31, 1 <= sims,
+ * 1 <= L <= 65535, 2 <= T, 1 <= cap <= 2^24 with M * cap * 64 inside int64, and no flag bit other
+ * than SPARC_PLAYOUT_FORWARD.  Every pointer is needed.  Device pointers, asynchronous on the
+ * context's stream. */
+#define SPARC_MCTS_INVALID 0
+#define SPARC_MCTS_DONE 1
+#define SPARC_MCTS_FULL 2
+#define SPARC_MCTS_PENDING 3
+#define SPARC_MCTS_DEAD_END 4
+#define SPARC_MCTS_NODE_BYTES 64
+#define SPARC_MCTS_NO_CHILD 0xFFFFFFFFu
+typedef struct {
+    uint8_t *status;
+    uint32_t *sims_done;
+    void *win_rec;
+    uint32_t *win_steps;
+} sparc_mcts_out;
+int sparc_mcts_device(void *ctx, const sparc_snapshot_info *info, const void *d_records, int64_t M,
+                      int32_t sims, int32_t L, uint64_t seed, uint64_t id0, uint32_t flags,
+                      const float *d_ep, const float *d_ec, int32_t T, int64_t cap, void *d_nodes,
+                      uint32_t *d_count, const sparc_mcts_out *out);
+/* the host-pointer form (everything on the host, no alignment requirement): staged through the
+ * context's stream, returns after the data have moved; nodes, count, win_rec and win_steps are
+ * read, updated and written back */
+int sparc_mcts_host(void *ctx, const sparc_snapshot_info *info, const void *records, int64_t M,
+                    int32_t sims, int32_t L, uint64_t seed, uint64_t id0, uint32_t flags,
+                    const float *ep, const float *ec, int32_t T, int64_t cap, void *nodes,
+                    uint32_t *count, const sparc_mcts_out *out);
+
 /* ---- debug: kernel variants (A/B runs and tests) ----------------------------------------------
  * Selects, for this context, among kernel variants that compute identical results.  Callers never
  * need it, and nothing else (no environment variable) changes the kernel a context runs.

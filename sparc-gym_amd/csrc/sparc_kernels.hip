@@ -14,6 +14,7 @@
 //   k_replay   given action sequences played from records or puzzle roots, without an env (sparc_replay.hpp)
 //   k_dfs      depth-first subtree search of state records with rule verdicts (sparc_dfs.hpp)
 //              and, as k_dfs<.., DfsLiveMoves>, over the moves that can still reach the target (sparc_dfs_prune.hpp)
+//   k_mcts     UCT tree search of state records, one resumable tree per record (sparc_mcts.hpp)
 // No MFMA: this is integer / bitboard work, bound by latency and HBM.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -40,6 +41,7 @@
 #include "sparc_replay.hpp"
 #include "sparc_rules_rec.hpp"
 #include "sparc_dfs.hpp"
+#include "sparc_mcts.hpp"
 #include "sparc_devbuf.hpp"
 #include "sparc_tables.hpp"
 #include "sparc_gym_amd.h"
@@ -2158,6 +2160,9 @@ struct Ctx {
     // counts [8M] | und_count | state [M] | und_root [cap] | status [M]
     DevBuf<uint8_t> df_rec, df_und;
     DevBuf<uint64_t> df_out;
+    // sparc_mcts_host (sparc_mcts.hpp): the arena, and ep | ec [T] | count | sims_done | win_steps [M] | status [M]
+    DevBuf<uint4> mc_nodes;
+    DevBuf<uint32_t> mc_out;
     DevBuf<uint16_t> s_bits;        // per-env audit outputs of the host-pointer / one-env calls
     DevBuf<uint8_t> s_region;
     DevBuf<uint64_t> s_fit;
@@ -4247,6 +4252,103 @@ int sparc_dfs_pruned_host(void* ctx, const sparc_snapshot_info* info, const void
     int rc = check_ctx(c, false);
     if (rc) return rc;
     return dfs_host(c, info, records, M, budget, prune, true, state, out);
+}
+
+// ---- UCT tree search of records (sparc_mcts.hpp): reads the context's tables only
+static int check_mcts_args(Ctx* c, const sparc_snapshot_info* info, const void* records, int64_t M, int32_t sims,
+                           int32_t L, uint32_t flags, const float* ep, const float* ec, int32_t T, int64_t cap,
+                           const void* nodes, const uint32_t* count, const sparc_mcts_out* out, bool device) {
+    int rc = check_snapshot_info(c, info);
+    if (rc) return rc;
+    if (!records) return fail(c, SPARC_E_INVALID, "null records");
+    if (M < 1 || M > 0x7FFFFFFFll) return fail(c, SPARC_E_INVALID, "M must be in 1..2^31-1");
+    if (sims < 1) return fail(c, SPARC_E_INVALID, "sims must be in 1..2^31-1");
+    if (L < 1 || L > 65535) return fail(c, SPARC_E_INVALID, "L must be in 1..65535");
+    if (flags & ~SPARC_PLAYOUT_FORWARD) return fail(c, SPARC_E_INVALID, "unknown bits in flags");
+    if (!ep || !ec) return fail(c, SPARC_E_INVALID, "null ep or ec");
+    if (T < 2) return fail(c, SPARC_E_INVALID, "T must be at least 2");
+    if (cap < 1 || cap > (1ll << 24)) return fail(c, SPARC_E_INVALID, "cap must be in 1..2^24");
+    if (M > INT64_MAX / SPARC_MCTS_NODE_BYTES / cap)
+        return fail(c, SPARC_E_INVALID, "M * cap * 64 must fit in int64");
+    if (!nodes) return fail(c, SPARC_E_INVALID, "null nodes");
+    if (!count) return fail(c, SPARC_E_INVALID, "null count");
+    if (!out) return fail(c, SPARC_E_INVALID, "null out");
+    if (!out->status || !out->sims_done || !out->win_rec || !out->win_steps)
+        return fail(c, SPARC_E_INVALID, "out: status, sims_done, win_rec and win_steps are all needed");
+    if (device) {
+        if ((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(out->win_rec)) & 15u)
+            return fail(c, SPARC_E_INVALID, "records and out->win_rec must be 16-B aligned");
+        if (reinterpret_cast<uintptr_t>(nodes) & 63u) return fail(c, SPARC_E_INVALID, "nodes must be 64-B aligned");
+        if ((reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(out->sims_done) |
+             reinterpret_cast<uintptr_t>(out->win_steps) | reinterpret_cast<uintptr_t>(ep) |
+             reinterpret_cast<uintptr_t>(ec)) & 3u)
+            return fail(c, SPARC_E_INVALID, "ep, ec, count, out->sims_done and out->win_steps must be 4-B aligned");
+    }
+    return SPARC_OK;
+}
+
+int sparc_mcts_device(void* ctx, const sparc_snapshot_info* info, const void* d_records, int64_t M, int32_t sims,
+                      int32_t L, uint64_t seed, uint64_t id0, uint32_t flags, const float* d_ep, const float* d_ec,
+                      int32_t T, int64_t cap, void* d_nodes, uint32_t* d_count, const sparc_mcts_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_mcts_args(c, info, d_records, M, sims, L, flags, d_ep, d_ec, T, cap, d_nodes, d_count, out, true)))
+        return rc;
+    const Params p = make_params(c);
+    const MctsOut o{out->status, out->sims_done, static_cast<uint4*>(out->win_rec), out->win_steps};
+    const dim3 gr((unsigned)(((uint64_t)M + kSnapBlock - 1) / kSnapBlock));
+    dispatch_w_tb(c->W, c->cfg.traceback, [&](auto w, auto tb) {
+        k_mcts<decltype(w)::value, decltype(tb)::value><<<gr, kSnapBlock, 0, c->stream>>>(
+            p, static_cast<const uint4*>(d_records), (uint32_t)M, (uint32_t)sims, (uint32_t)L, seed, id0, flags, d_ep,
+            d_ec, (uint32_t)T, (uint32_t)cap, static_cast<uint4*>(d_nodes), d_count, o);
+    });
+    return launch_check(c);
+}
+
+int sparc_mcts_host(void* ctx, const sparc_snapshot_info* info, const void* records, int64_t M, int32_t sims, int32_t L,
+                    uint64_t seed, uint64_t id0, uint32_t flags, const float* ep, const float* ec, int32_t T,
+                    int64_t cap, void* nodes, uint32_t* count, const sparc_mcts_out* out) {
+    DevGuard dg;
+    Ctx* c = static_cast<Ctx*>(ctx);
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    if ((rc = check_mcts_args(c, info, records, M, sims, L, flags, ep, ec, T, cap, nodes, count, out, false)))
+        return rc;
+    const size_t m = (size_t)M, t = (size_t)T, rbytes = (size_t)info->record_bytes * m;
+    const size_t nbytes = m * (size_t)cap * SPARC_MCTS_NODE_BYTES;
+    // u32 words: ep [T] | ec [T] | count [m] | sims_done [m] | win_steps [m] | status [m] u8;
+    // fk_rec: the records | the winners
+    const size_t w_count = 2 * t, w_done = w_count + m, w_steps = w_done + m, w_status = w_steps + m,
+                 words = w_status + (m + 3) / 4;
+    HIPCHK(c, c->fk_rec.reserve(2 * rbytes));
+    HIPCHK(c, c->mc_nodes.reserve(nbytes / sizeof(uint4)));
+    HIPCHK(c, c->mc_out.reserve(words));
+    uint32_t* o32 = c->mc_out.get();
+    float* d_ep = reinterpret_cast<float*>(o32);
+    sparc_mcts_out d{};
+    d.status = reinterpret_cast<uint8_t*>(o32 + w_status);
+    d.sims_done = o32 + w_done;
+    d.win_rec = c->fk_rec.get() + rbytes;
+    d.win_steps = o32 + w_steps;
+    HIPCHK(c, hipMemcpyAsync(c->fk_rec.get(), records, rbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d.win_rec, out->win_rec, rbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ep, ep, 4 * t, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ep + t, ec, 4 * t, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(o32 + w_count, count, 4 * m, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d.win_steps, out->win_steps, 4 * m, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->mc_nodes.get(), nodes, nbytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = sparc_mcts_device(c, info, c->fk_rec.get(), M, sims, L, seed, id0, flags, d_ep, d_ep + t, T, cap,
+                                c->mc_nodes.get(), o32 + w_count, &d)))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(nodes, c->mc_nodes.get(), nbytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(count, o32 + w_count, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->status, d.status, m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->sims_done, d.sims_done, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->win_rec, d.win_rec, rbytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out->win_steps, d.win_steps, 4 * m, hipMemcpyDeviceToHost, c->stream));
+    return sparc_sync(c);
 }
 
 // ---- rule audit of records (sparc_rules_rec.hpp): reads the context's tables only

@@ -143,6 +143,25 @@ class SparcDfsOut(ctypes.Structure):
                                         "und_count")] + [("und_cap", c_uint64)]
 
 
+# SPARC_MCTS_*: the status of a root's tree after sparc_mcts_device
+MCTS_INVALID, MCTS_DONE, MCTS_FULL, MCTS_PENDING, MCTS_DEAD_END = range(5)
+MCTS_NODE_WORDS = 16            # SPARC_MCTS_NODE_BYTES / 4: a node is 16 uint32
+MCTS_NO_CHILD = 0xFFFFFFFF      # SPARC_MCTS_NO_CHILD: child[a] of an action that is not a child
+MCTS_MAX_CAP = 1 << 24          # the largest arena per root, in nodes
+# the words of a node: w0 parent | action << 28 | kind << 30, then visits, wins, losses, child[4], n[4], wins[4]
+MCTS_VISITS, MCTS_WINS, MCTS_LOSSES, MCTS_CHILD, MCTS_N, MCTS_CHILD_WINS = 1, 2, 3, 4, 8, 12
+MCTS_KIND_INNER, MCTS_KIND_TERMINATED, MCTS_KIND_TRUNCATED, MCTS_KIND_DEAD_END = range(4)
+
+
+class SparcMctsOut(ctypes.Structure):
+    """sparc_mcts_out: the outputs of sparc_mcts_device / _host, all needed."""
+    _fields_ = [(k, c_void_p) for k in ("status", "sims_done", "win_rec", "win_steps")]
+
+
+_MCTS_ARGS = [c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64, c_int32, c_int32, c_uint64,
+              c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_int32, ctypes.c_int64, c_void_p, c_void_p,
+              ctypes.POINTER(SparcMctsOut)]
+
 _SIGS = {
     "sparc_abi_version": ([], c_int32),
     "sparc_last_error": ([c_void_p], ctypes.c_char_p),
@@ -212,6 +231,8 @@ _SIGS = {
                                  ctypes.c_uint32, c_int32, c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
     "sparc_dfs_pruned_host": ([c_void_p, ctypes.POINTER(SparcSnapshotInfo), c_void_p, ctypes.c_int64,
                                ctypes.c_uint32, c_int32, c_void_p, ctypes.POINTER(SparcDfsOut)], c_int32),
+    "sparc_mcts_device": (_MCTS_ARGS, c_int32),
+    "sparc_mcts_host": (_MCTS_ARGS, c_int32),
     "sparc_load_rules": ([c_void_p, ctypes.POINTER(SparcRulesTable)], c_int32),
     "sparc_rules_device": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),
     "sparc_rules_host": ([c_void_p, c_void_p, c_void_p, c_void_p], c_int32),

@@ -593,6 +593,74 @@ class SparcCore:
             out.update(undecided=und[:n], undecided_root=root[:n], undecided_total=int(count[0]))
         return out
 
+    # ---------------------------------------------------------------- UCT tree search of records
+    @staticmethod
+    def _check_mcts(M, sims, L, flags, T, cap):
+        """The argument rules of sparc_mcts_device that need no device (ValueError naming the argument)."""
+        if not 1 <= M < 2**31:
+            raise ValueError("M must be in 1..2^31-1")
+        if not 1 <= sims < 2**31:
+            raise ValueError("sims must be in 1..2^31-1")
+        if not 1 <= L <= 65535:
+            raise ValueError("L (the horizon) must be in 1..65535")
+        if flags & ~_lib.PLAYOUT_FORWARD:
+            raise ValueError("unknown bits in flags")
+        if T < 2:
+            raise ValueError("T (the entries of ep and ec) must be at least 2")
+        if not 1 <= cap <= _lib.MCTS_MAX_CAP:
+            raise ValueError("cap must be in 1..2^24")
+        if M * cap * 4 * _lib.MCTS_NODE_WORDS >= 2**63:
+            raise ValueError("M * cap * 64 must fit in int64")
+
+    def mcts_device(self, info, d_records, M, sims, L, d_ep, d_ec, T, cap, d_nodes, d_count, d_status, d_sims_done,
+                    d_win_rec, d_win_steps, seed=0, id0=0, flags=0):
+        """sparc_mcts_device: ``sims`` UCT simulations on the tree of each of M records, the trees in
+        the arena d_nodes [M][cap] of 64-byte nodes with d_count [M] uint32 in use (in/out; 0: a fresh
+        tree); ep, ec [T] float32 the exploration tables; status [M] uint8, sims_done [M] uint32,
+        win_rec [M] records and win_steps [M] uint32 (both in/out), all needed; reads the context's
+        tables only (asynchronous)."""
+        M, sims, L, T, cap, flags = int(M), int(sims), int(L), int(T), int(cap), int(flags)
+        self._check_mcts(M, sims, L, flags, T, cap)
+        out = _lib.SparcMctsOut(d_status, d_sims_done, d_win_rec, d_win_steps)
+        self._check(self.lib.sparc_mcts_device(self.ctx, ctypes.byref(info), d_records, M, sims, L,
+                                               int(seed) & (2**64 - 1), int(id0) & (2**64 - 1), flags, d_ep, d_ec, T,
+                                               cap, d_nodes, d_count, ctypes.byref(out)))
+
+    def mcts_host(self, info, records, sims, L, ep, ec, cap, nodes=None, count=None, win=None, win_steps=None,
+                  seed=0, id0=0, flags=0):
+        """Search host records [M, record_bytes] (synchronous): a dict of host arrays ``status`` [M]
+        uint8, ``sims`` [M] uint32 (this call's), ``nodes`` [M, cap, 16] uint32, ``count`` [M] uint32,
+        ``win`` [M, record_bytes] uint8 and ``win_steps`` [M] uint32.  ``nodes``, ``count``, ``win``
+        and ``win_steps`` of a previous call are continued in place; fresh ones (zeroed, win_steps
+        0xFFFFFFFF) otherwise."""
+        rec = np.ascontiguousarray(records, np.uint8)
+        if rec.ndim != 2 or rec.shape[1] != info.record_bytes or len(rec) < 1:
+            raise ValueError(f"records must be [M, {info.record_bytes}] uint8 with M >= 1")
+        ep, ec = np.ascontiguousarray(ep, np.float32), np.ascontiguousarray(ec, np.float32)
+        if ep.ndim != 1 or ep.shape != ec.shape:
+            raise ValueError("ep and ec must be one-dimensional float32 arrays of the same length T")
+        M, sims, L, T, cap, flags = len(rec), int(sims), int(L), len(ep), int(cap), int(flags)
+        self._check_mcts(M, sims, L, flags, T, cap)
+
+        def arg(a, shape, dtype, what, fill=0):
+            if a is None:
+                return np.full(shape, fill, dtype)
+            if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError(f"{what} must be a C-contiguous {np.dtype(dtype).name} array {list(shape)}")
+            return a
+
+        nodes = arg(nodes, (M, cap, _lib.MCTS_NODE_WORDS), np.uint32, "nodes")
+        count = arg(count, (M,), np.uint32, "count")
+        win = arg(win, rec.shape, np.uint8, "win")
+        win_steps = arg(win_steps, (M,), np.uint32, "win_steps", 0xFFFFFFFF)
+        out = {"status": np.empty(M, np.uint8), "sims": np.empty(M, np.uint32), "nodes": nodes, "count": count,
+               "win": win, "win_steps": win_steps}
+        o = _lib.SparcMctsOut(_ptr(out["status"]), _ptr(out["sims"]), _ptr(win), _ptr(win_steps))
+        self._check(self.lib.sparc_mcts_host(self.ctx, ctypes.byref(info), _ptr(rec), M, sims, L,
+                                             int(seed) & (2**64 - 1), int(id0) & (2**64 - 1), flags, _ptr(ep),
+                                             _ptr(ec), T, cap, _ptr(nodes), _ptr(count), ctypes.byref(o)))
+        return out
+
 
 def visited_planes(bits, table: PuzzleTable, x_dim=None, y_dim=None):
     """Decode visited bitboards [words][N] into int32 planes [N][x_dim][y_dim] (host)."""

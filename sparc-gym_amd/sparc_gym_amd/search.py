@@ -194,6 +194,55 @@ def monte_carlo(vec, snap, playouts, horizon, seed=0, forward_only=None):
             "solution": solution}
 
 
+def uct(vec, snap, sims, horizon, c=1.0, trees=1, explore=None, seed=0, forward_only=None, tree=None, cap=None):
+    """UCT search of every record of ``snap`` (M of them) with ``vec.mcts``: ``sims`` simulations on
+    each of ``trees`` independent trees per record in ONE launch.  Record ``j`` is repeated
+    ``trees`` times (rows ``j * trees .. j * trees + trees - 1`` of the search), the rows are
+    distinct and so are their random streams: root parallelism.  ``tree``: the ``tree`` of a previous
+    call with the same ``snap`` and ``trees``, to continue it; ``cap``, ``c``, ``explore``, ``seed``
+    and ``forward_only`` as ``vec.mcts``.  Touches no env.
+
+    Returns a dict: ``visits``, ``wins``, ``losses`` [M, 4] int64 numpy arrays, the roots' per-action
+    ``n``, ``wins`` and the children's own losses summed over the trees; ``best_action`` [M] int64,
+    the most visited action (ties go to the lowest action), -1 where no action has a visit (a root
+    that is done, walled in or refused); ``solution``: per record the action list, from the puzzle's
+    start, of the shortest winning path its trees have found (the lowest tree wins ties), or None
+    (always None without traceback: such records hold no moves); ``status`` [M, trees] and
+    ``tree``: what ``vec.mcts`` returned for the ``M * trees`` rows."""
+    from . import _lib
+    M, trees = len(snap), int(trees)
+    if M < 1 or trees < 1:
+        raise ValueError("at least one record and one tree are needed")
+    rows = torch.arange(M * trees) // trees
+    out = vec.mcts(snap.select(rows), sims, horizon, c=c, explore=explore, tree=tree, cap=cap, seed=seed,
+                   forward_only=forward_only)
+    nodes = out["nodes"].view(torch.int32)                                     # [M * trees, cap, 16]
+    root = nodes[:, 0].to(torch.int64) & 0xFFFFFFFF
+    child = root[:, _lib.MCTS_CHILD:_lib.MCTS_CHILD + 4]
+    real = (child != 0) & (child < nodes.shape[1])                             # (MCTS_NO_CHILD lies above every cap)
+    own = torch.gather(nodes[:, :, _lib.MCTS_LOSSES], 1, torch.where(real, child, torch.zeros_like(child)))
+    own = own.to(torch.int64) & 0xFFFFFFFF
+    started = (out["count"] > 0)[:, None]                                      # an untouched arena holds no root
+
+    def total(x):
+        return torch.where(started, x, torch.zeros_like(x)).reshape(M, trees, 4).sum(1).cpu().numpy()
+
+    visits = total(root[:, _lib.MCTS_N:_lib.MCTS_N + 4])
+    wins = total(root[:, _lib.MCTS_CHILD_WINS:_lib.MCTS_CHILD_WINS + 4])
+    losses = total(torch.where(real, own, torch.zeros_like(own)))
+    best = np.where((visits > 0).any(1), visits.argmax(1), -1).astype(np.int64)   # argmax: the first maximum
+    steps = out["win_steps"].reshape(M, trees).cpu().numpy()
+    solution = [None] * M
+    if vec.traceback:
+        won = np.nonzero((steps >= 0).any(1))[0]
+        k = np.where(steps >= 0, steps, np.iinfo(np.int64).max).argmin(1)         # the first minimum
+        if len(won):
+            for j, path in zip(won, out["win"].select(torch.as_tensor(won * trees + k[won])).moves()):
+                solution[j] = path
+    return {"visits": visits, "wins": wins, "losses": losses, "best_action": best, "solution": solution,
+            "status": out["status"].reshape(M, trees), "tree": out}
+
+
 ILLEGAL_ACTION = 255   # an action value no state accepts (any value above 3 is illegal)
 
 

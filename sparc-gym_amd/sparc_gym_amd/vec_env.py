@@ -44,6 +44,8 @@ into two channels of the network's input tensor, with ``puzzle_index``, ``agent_
 ``reach(snap, plane)`` tells for records whether the free lattice points still connect the agent to the
 target, the distance to it overall and through each action, and optionally the distance plane, again in
 one launch without an env (``search.expand_frontier(..., prune=True)``).
+``mcts(snap, sims, horizon)`` grows a UCT search tree per record, kept on the GPU between calls and
+resumable, again in one launch without an env (``search.uct``).
 """
 from __future__ import annotations
 
@@ -357,7 +359,119 @@ class _RecordReach:
         return out
 
 
-class SPaRCVecEnv(_RecordReplay, _RecordObserve, _RecordReach):
+def uct_tables(c=1.0, entries=4096):
+    """The default exploration tables of ``mcts``: ``ep[n] = c * sqrt(ln max(n, 1))`` over the
+    node's visits and ``ec[n] = 1 / sqrt(max(n, 1))`` over the child's, so that ``ep * ec`` is UCT's
+    ``c * sqrt(ln N / n)``; computed in float64, then rounded to float32.  Indices past the last
+    entry read the last one.  Returns two numpy float32 arrays [entries]."""
+    entries = int(entries)
+    if entries < 2:
+        raise ValueError("entries must be at least 2")
+    n = np.maximum(np.arange(entries, dtype=np.float64), 1.0)
+    return (float(c) * np.sqrt(np.log(n))).astype(np.float32), (1.0 / np.sqrt(n)).astype(np.float32)
+
+
+class _RecordMcts:
+    """``mcts`` of ``SPaRCVecEnv``: the UCT tree search of records.  A base class of its own for the
+    reason ``_RecordReplay`` is one; tests/test_mcts_guards.py and tests/test_gpu_mcts.py check the
+    stream contract for it."""
+
+    def mcts(self, snap, sims, horizon, c=1.0, explore=None, tree=None, cap=None, seed=0, id0=0, forward_only=None):
+        """``sims`` UCT simulations on a search tree of every record of ``snap`` (M roots), in one
+        launch and without changing or reading any env (k_mcts): selection by
+        ``wins / n + ep[visits] * ec[n]`` over the forward moves (the legal actions without the
+        traceback pop, ``dfs``'s children), one new node per simulation, a legal-move rollout of at
+        most ``horizon`` steps from it (``playout``'s, drawn with id ``id0 + j * 2**32 + s`` for
+        simulation ``s`` of root ``j``; ``forward_only``, by default ``self.traceback``, keeps the
+        pop out of it), and the backup of the last step's reward code (+100 a win, -100 a loss).
+
+        ``explore=(ep, ec)``: two float32 tables of the same length T >= 2, finite, indexed by
+        ``min(visits, T - 1)`` of the node and ``min(n, T - 1)`` of the child; default
+        ``uct_tables(c)``.  ``tree``: the dict a previous call returned, to continue its trees (same
+        ``snap``; k calls of S simulations give what one call of k * S gives, byte for byte).
+        ``cap``: the nodes per root of a fresh arena (default ``sims + 1``, which is always enough),
+        or of a larger arena the given tree is copied into first.
+
+        Returns a dict on the GPU: ``status`` [M] uint8 (``_lib.MCTS_*``: 0 refused, 1 done, 2 the
+        arena is full or the root's visits are at their limit, 3 the record was already done, 4 it
+        is live without a forward move), ``sims`` [M] int32 the simulations of this call,
+        ``nodes`` [M, cap, 16] uint32 and ``count`` [M] int32 the trees (the node layout:
+        INTEGRATION.md), ``win`` a ``Snapshot`` of the shortest winning end state per root and
+        ``win_steps`` [M] int64 its steps from the root, -1 where none was found (``win`` is zeroed
+        there).  A root that fails the kernel's checks (a bad record, a damaged tree) gets status 0,
+        and the next ``core.sync()`` raises.  ValueError naming the argument otherwise."""
+        from .snapshot import Snapshot, info_mismatch
+        self._stream()
+        bad = info_mismatch(snap.info, self.core.snapshot_info())
+        if bad is not None:
+            raise ValueError(f"snapshot does not match this env: {bad} differs")
+        M, sims, L = len(snap), int(sims), int(horizon)
+        if forward_only is None:
+            forward_only = bool(self.traceback)
+        dev, rb = self.device, snap.info.record_bytes
+        if tree is None:
+            cap = sims + 1 if cap is None else int(cap)
+        else:
+            old = tree["nodes"]
+            if not (isinstance(old, torch.Tensor) and old.dtype == torch.uint32 and old.ndim == 3 and
+                    old.shape[0] == M and old.shape[2] == _lib.MCTS_NODE_WORDS and old.is_contiguous() and
+                    old.device == dev):
+                raise ValueError(f"tree['nodes'] must be a contiguous uint32 tensor [{M}, cap, 16] on {dev}")
+            cap = int(old.shape[1]) if cap is None else int(cap)
+            if cap < old.shape[1]:
+                raise ValueError("cap must not be below the given tree's")
+        if explore is None:
+            ep, ec = uct_tables(c)
+        else:
+            try:
+                ep, ec = (np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a,
+                                               np.float32) for a in explore)
+            except (TypeError, ValueError):
+                raise ValueError("explore must be two float32 tables (ep, ec)") from None
+            if ep.ndim != 1 or ep.shape != ec.shape:
+                raise ValueError("explore: ep and ec must be one-dimensional and of the same length")
+            if not (np.isfinite(ep).all() and np.isfinite(ec).all()):
+                raise ValueError("explore: ep and ec must be finite")
+        SparcCore._check_mcts(M, sims, L, 0, len(ep), cap)
+        rec = snap.records
+        if not isinstance(rec, torch.Tensor):
+            rec = torch.from_numpy(np.ascontiguousarray(rec, np.uint8))
+        rec = rec.to(dev).contiguous()
+        if tree is None:
+            nodes = torch.zeros((M, cap, _lib.MCTS_NODE_WORDS), dtype=torch.int32, device=dev)
+            count = torch.zeros(M, dtype=torch.int32, device=dev)
+            win = torch.zeros((M, rb), dtype=torch.uint8, device=dev)
+            wsteps = torch.full((M,), -1, dtype=torch.int32, device=dev)
+        else:
+            nodes = old.view(torch.int32)
+            if cap > nodes.shape[1]:
+                grown = torch.zeros((M, cap, _lib.MCTS_NODE_WORDS), dtype=torch.int32, device=dev)
+                grown[:, :nodes.shape[1]] = nodes
+                nodes = grown
+            count, win, wsteps = tree["count"], tree["win"], tree["win_steps"]
+            win = win.records if isinstance(win, Snapshot) else win
+            if not (isinstance(count, torch.Tensor) and count.dtype == torch.int32 and tuple(count.shape) == (M,) and
+                    count.is_contiguous() and count.device == dev):
+                raise ValueError(f"tree['count'] must be a contiguous int32 tensor [{M}] on {dev}")
+            if not (isinstance(win, torch.Tensor) and win.dtype == torch.uint8 and tuple(win.shape) == (M, rb) and
+                    win.is_contiguous() and win.device == dev):
+                raise ValueError(f"tree['win'] must hold contiguous uint8 records [{M}, {rb}] on {dev}")
+            if not (isinstance(wsteps, torch.Tensor) and tuple(wsteps.shape) == (M,) and
+                    not wsteps.dtype.is_floating_point and wsteps.device == dev):
+                raise ValueError(f"tree['win_steps'] must be an integer tensor [{M}] on {dev}")
+            wsteps = wsteps.to(torch.int32).contiguous()      # -1 is the kernel's 0xFFFFFFFF
+        tab = torch.from_numpy(np.stack([ep, ec])).to(dev)    # [2, T]
+        status = torch.empty(M, dtype=torch.uint8, device=dev)
+        done = torch.empty(M, dtype=torch.int32, device=dev)
+        self.core.mcts_device(snap.info, rec.data_ptr(), M, sims, L, tab[0].data_ptr(), tab[1].data_ptr(), len(ep), cap,
+                              nodes.data_ptr(), count.data_ptr(), status.data_ptr(), done.data_ptr(), win.data_ptr(),
+                              wsteps.data_ptr(), seed=seed, id0=id0,
+                              flags=_lib.PLAYOUT_FORWARD if forward_only else 0)
+        return {"status": status, "sims": done, "nodes": nodes.view(torch.uint32), "count": count,
+                "win": Snapshot(win, snap.info), "win_steps": wsteps.to(torch.int64)}
+
+
+class SPaRCVecEnv(_RecordReplay, _RecordObserve, _RecordReach, _RecordMcts):
     def __init__(self, num_envs, puzzles=None, df_name="lkaesberg/SPaRC", df_split="all", df_set="test",
                  observation="new", traceback=False, max_steps=2000, autoreset="next_step", device=0,
                  env_offset=0, pitch=None, words=None, processed=None, table=None, rules=False, copy=True,
